@@ -3,7 +3,16 @@
 of one full Trainer.train_step (forward, backward, grad all-reduce, clip,
 Adam, StepLR, EMA codebook) on synthetic 80-dim mel batches.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds every other measurement to that line: the dominant kernel's
+roofline (per-launch probe inside the timed region), the read-loss loop, the
+VQ kernel line, the fp32 line and the CPU baseline (--no-probe,
+--no-read-loss, --vq-reps 0, --fp32-steps 0, --no-cpu-baseline drop single
+legs of it).  --dump-outputs DIR writes what the last timed step left its
+caller (loss_detail, codebook, a fixed sample of the updated parameters) as
+DIR/<name>.npy; with the same arguments the inputs are the same every run.
 
 N > 1: one rank per GPU (RCCL over xGMI); each rank trains 64 x 256 frames
 (weak scaling, global batch 64*N).  Under torch.distributed.run (WORLD_SIZE
@@ -45,6 +54,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--config", default="vcc20", choices=["vcc20", "aishell3"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline probe, the read-loss loop, the VQ line, the fp32 line and the "
+                         "CPU baseline (a plain run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss_detail, codebook, a seeded sample of the "
+                         "updated parameters) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--fp32-steps", type=int, default=5,
@@ -65,7 +80,33 @@ def parse():
                     help="skip the second timed loop that reads loss_detail every step (ms_per_step_read_loss)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="N>1 process group (nccl = RCCL; gloo lets tests run several ranks on one GPU)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:  # a plain run: the timed steps only
+        a.no_probe, a.read_loss, a.no_cpu_baseline = True, False, True
+        a.vq_reps = a.fp32_steps = 0
+    return a
+
+
+DUMP_PARAM_SAMPLE = 1 << 22     # --dump-outputs: parameters sampled (16 MB of float32)
+
+
+def dump_outputs(path, tr, det):
+    """--dump-outputs: what the last timed step left its caller, one .npy each:
+    every loss_detail value (float64), the codebook (float32) and a fixed,
+    seeded sample of the updated flat parameter vector (float32)."""
+    os.makedirs(path, exist_ok=True)
+    for k, v in dict(det).items():
+        np.save(os.path.join(path, "loss_" + "_".join(k.split()) + ".npy"), np.asarray([v], dtype=np.float64))
+    np.save(os.path.join(path, "codebook.npy"),
+            tr.model.quantizer.embeddings.detach().float().cpu().numpy())
+    flat = tr.engine.flat_p.detach()
+    n = flat.numel()
+    if n > DUMP_PARAM_SAMPLE:
+        idx = np.sort(np.random.default_rng(20240).integers(0, n, size=DUMP_PARAM_SAMPLE))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(path, "params.npy"), flat.float().cpu().numpy())
 
 
 def cpu_baseline(cfg, steps):
@@ -336,6 +377,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     detail = dict(det)
+    if a.dump_outputs and rank == 0:  # before any further step moves the weights on
+        dump_outputs(a.dump_outputs, tr, det)
     # the same loop as a recipe runs it: the reference's bin/train.py:128-132
     # appends every loss_detail value every iteration, so each step ends in a
     # host read of the step's statistics (one device sync per step)
@@ -369,6 +412,7 @@ def main():
         "metric": "mel-frames/sec/GPU VQ-VAE train step (80-dim mel, batch=64x256f) at 1/2/4/8 GPUs",
         "value": round(value, 1), "unit": "mel-frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "full": a.full,
         "ms_per_step_read_loss": None if read_ms is None else round(read_ms, 3),
         "read_loss_overhead": None if read_ms is None else round(read_ms / ms - 1.0, 4),
         "dtype": a.dtype, "data": "synthetic (N(0,1) 80-mel, random speaker ids; seeded random-init weights)",

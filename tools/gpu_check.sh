@@ -11,7 +11,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
   > $O/tests_all.log 2>&1 || { tail -40 $O/tests_all.log; exit 1; }
 tail -1 $O/tests_all.log
 for i in 1 2; do
-  timeout -k 10 200 python -u bench.py --no-cpu-baseline --fp32-steps 0 > $O/bench_probe$i.json 2> $O/bench_probe$i.err || exit $?
+  timeout -k 10 200 python -u bench.py --full --no-cpu-baseline --fp32-steps 0 > $O/bench_probe$i.json 2> $O/bench_probe$i.err || exit $?
   timeout -k 10 200 python -u bench.py --no-cpu-baseline --fp32-steps 0 --vq-reps 0 --no-probe > $O/bench_noprobe$i.json 2> $O/bench_noprobe$i.err || exit $?
 done
 python3 - <<'PY'

@@ -14,14 +14,14 @@ if [ "$PART" = 1 ]; then
   timeout -k 10 1000 python -u -m pytest tests -m gpu -q -rs --timeout 600 --timeout-method thread > $O/gpu_tests.log 2>&1
   rc=$?; tail -2 $O/gpu_tests.log; [ $rc -ne 0 ] && { grep -E "FAILED|Error" $O/gpu_tests.log | head; exit $rc; }
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail $O/smoke.log; exit 1; }
-  timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+  timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
   cut -c1-300 $O/bench.json
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py \
-    --no-cpu-baseline --no-read-loss > $O/prof.log 2>&1 || exit 1
+    --full --no-cpu-baseline --no-read-loss > $O/prof.log 2>&1 || exit 1
   python3 tools/trace_steps.py $O/prof/run_kernel_trace.csv 45 > $O/rocprof_summary.txt && head -14 $O/rocprof_summary.txt
   # the one-stream schedule the bench's probed steps use (the roofline kernel's own launch durations)
   VQX_ENGINE='{"bwd_streams": false}' timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof1 -o run \
-    --output-format csv -- python3 bench.py --no-cpu-baseline --no-read-loss > $O/prof1.log 2>&1 || exit 1
+    --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-read-loss > $O/prof1.log 2>&1 || exit 1
   python3 tools/trace_steps.py $O/prof1/run_kernel_trace.csv 45 > $O/rocprof_summary_one_stream.txt && head -4 $O/rocprof_summary_one_stream.txt
 else
   bash tools/gpu_pmc_hbm.sh $TAG || exit 1

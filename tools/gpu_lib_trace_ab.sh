@@ -14,6 +14,6 @@ timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeout-method threa
 for side in new old; do
   lib=""; [ $side = old ] && lib=$OLD
   VQX_LIB="$lib" timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/p_$side -o run --output-format csv -- \
-    python3 bench.py --no-cpu-baseline --fp32-steps 0 --vq-reps 0 --steps 20 > $O/log_$side.txt 2>&1 || exit 1
+    python3 bench.py --full --no-cpu-baseline --fp32-steps 0 --vq-reps 0 --steps 20 > $O/log_$side.txt 2>&1 || exit 1
 done
 bash tools/gpu_lib_step_ab.sh $TAG "$OLD"

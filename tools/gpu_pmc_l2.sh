@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/$TAG/pmc_l2
 mkdir -p $O
-P="python3 bench.py --steps 2 --warmup 1 --no-probe --no-cpu-baseline"
+P="python3 bench.py --full --steps 2 --warmup 1 --no-probe --no-cpu-baseline"
 timeout -s KILL 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum -d $O/p -o run --output-format csv -- $P > $O/p.log 2>&1 || exit $?
 python3 - $O <<'PY'
 import csv, collections, sys

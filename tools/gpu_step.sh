@@ -14,7 +14,7 @@ if [ $# -gt 0 ]; then
 fi
 timeout -k 10 600 python -u -m pytest -x -q --timeout 120 --timeout-method thread -m gpu tests > $O/tests.log 2>&1
 rc=$?; echo "tests rc=$rc"; tail -3 $O/tests.log; [ $rc -ne 0 ] && exit $rc
-VQX_BENCH_KERNELS=2 timeout -k 10 300 python bench.py --no-cpu-baseline --fp32-steps 0 --vq-reps 0 > $O/bench.json 2> $O/bench.err || exit $?
+VQX_BENCH_KERNELS=2 timeout -k 10 300 python bench.py --full --no-cpu-baseline --fp32-steps 0 --vq-reps 0 > $O/bench.json 2> $O/bench.err || exit $?
 cut -c1-400 $O/bench.json
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --no-cpu-baseline --fp32-steps 0 --vq-reps 0 > $O/prof.log 2>&1 || exit $?
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline --fp32-steps 0 --vq-reps 0 > $O/prof.log 2>&1 || exit $?
 python3 tools/trace_steps.py $O/prof/run_kernel_trace.csv > $O/trace_summary.txt 2>&1; head -24 $O/trace_summary.txt
