@@ -718,8 +718,46 @@ int vqx_mailbox_destroy(void* host);
 int vqx_mailbox_publish(const float* src, int32_t n, float* dev_copy, void* box_dev, int32_t slot, int32_t slots,
                         int32_t floats, uint32_t seq, vqx_stream_t stream);
 
+/*
+ * Style-token (GST) layer of the hierarchical model's top-level quantizer
+ * (ABI 129; model/layers_gst.py:10-147, called as layer(z.mean(dim=-1)) at
+ * vqvae2.py:97): a 1-query x N-token multi-head attention over
+ * tanh(gst_embs) with q/k/v/out linears, fp32 throughout.
+ *   ref[b]  = mean_t z[b*T + t][0..R)            (T = 1: forward(ref_embs))
+ *   tok     = tanh(gst_embs) [N][E];  K = tok Wk^T + bk;  V = tok Wv^T + bv
+ *   q[b]    = ref[b] Wq^T + bq;       per head h of width d_k = F / H:
+ *   a[b][h] = softmax_n(q_h . K[n]_h / sqrt(d_k));  ctx_h = sum_n a[n] V[n]_h
+ *   style[b] = ctx[b] Wo^T + bo                                    [B][F]
+ * vqx_gst_fwd: 2 launches (K/V per token; pool + attention per batch row),
+ * saving tok, K, V, ref, q, a, ctx in `ws`.  vqx_gst_bwd: 3 launches from
+ * d_style and the `ws` the forward filled; every gradient is overwritten
+ * (dz[b*T + t] = d_ref[b] / T on every frame; dbk is written as zeros: the
+ * softmax is invariant to a per-head constant).  Every sum over B, T, N runs
+ * in a fixed order without atomics: two runs give the same bits.
+ * Weights are nn.Linear's [out][in]: wq [F][R], wk / wv [F][E], wo [F][F].
+ * Limits (else -1): B, T >= 1; R % 4 == 0, R <= 512; 1 <= N <= 32; F % H == 0,
+ * F <= 512, d_k <= 128; E >= 1; ldz, lddz >= R; the pointers each call reads
+ * or writes non-NULL.  `ws` holds >= vqx_gst_workspace(...) floats.
+ */
+typedef struct {
+  const float* z;        /* [B*T][ldz] frame-major, R columns used       */
+  const float* gst_embs; /* [N][E]                                       */
+  const float *wq, *bq, *wk, *bk, *wv, *bv, *wo, *bo;
+  float* style;          /* fwd out [B][F]                               */
+  float* ws;             /* workspace, fwd writes / bwd reads + scratch  */
+  const float* d_style;  /* bwd in [B][F]                                */
+  float* dz;             /* bwd out [B*T][lddz]                          */
+  float* d_gst_embs;     /* bwd out, shapes of the parameters            */
+  float *dwq, *dbq, *dwk, *dbk, *dwv, *dbv, *dwo, *dbo;
+  int32_t B, T, R, N, E, F, H, ldz, lddz;
+} vqx_gst_args;
+/* Host-only size query (floats) of the workspace of one forward + backward. */
+int vqx_gst_workspace(int32_t B, int32_t N, int32_t F, int32_t H, int32_t R, int32_t E, int64_t* floats);
+int vqx_gst_fwd(const vqx_gst_args* a, vqx_stream_t stream);
+int vqx_gst_bwd(const vqx_gst_args* a, vqx_stream_t stream);
+
 /* ABI version (major*100 + minor); VQX_ABI_VERSION is what this header describes. */
-#define VQX_ABI_VERSION 128
+#define VQX_ABI_VERSION 129
 int vqx_version(void);
 
 #ifdef __cplusplus

@@ -15,7 +15,7 @@ from pathlib import Path
 import torch  # noqa: F401  (loads the HIP runtime first; see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libvqx.so"
-ABI_VERSION = 128  # include/vqx.h VQX_ABI_VERSION
+ABI_VERSION = 129  # include/vqx.h VQX_ABI_VERSION
 
 VQX_F32, VQX_BF16 = 0, 1
 PRO_NONE, PRO_LRELU, PRO_RELU, PRO_SCALE_RELU = 0, 1, 2, 3
@@ -72,6 +72,18 @@ class StepClose(ctypes.Structure):  # include/vqx.h vqx_step_close
                 ("pub_src", c_void_p), ("pub_n", c_int32), ("pub_copy", c_void_p), ("pub_box", c_void_p),
                 ("pub_slot", c_int32), ("pub_slots", c_int32), ("pub_floats", c_int32), ("pub_seq", ctypes.c_uint32),
                 ("rows_src", c_void_p), ("rows_ld", c_int32), ("n_rows", c_int32), ("rows_host", c_void_p)]
+
+
+class GstArgs(ctypes.Structure):  # include/vqx.h vqx_gst_args
+    _fields_ = [
+        ("z", c_void_p), ("gst_embs", c_void_p), ("wq", c_void_p), ("bq", c_void_p), ("wk", c_void_p),
+        ("bk", c_void_p), ("wv", c_void_p), ("bv", c_void_p), ("wo", c_void_p), ("bo", c_void_p),
+        ("style", c_void_p), ("ws", c_void_p), ("d_style", c_void_p), ("dz", c_void_p), ("d_gst_embs", c_void_p),
+        ("dwq", c_void_p), ("dbq", c_void_p), ("dwk", c_void_p), ("dbk", c_void_p), ("dwv", c_void_p),
+        ("dbv", c_void_p), ("dwo", c_void_p), ("dbo", c_void_p),
+        ("B", c_int32), ("T", c_int32), ("R", c_int32), ("N", c_int32), ("E", c_int32), ("F", c_int32),
+        ("H", c_int32), ("ldz", c_int32), ("lddz", c_int32),
+    ]
 
 
 WN_COLREDUCE = 2
@@ -175,6 +187,9 @@ _SIGS = {
     "vqx_adam_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p],
     "vqx_radam_hyper": [c_void_p, c_double, c_double, c_int32, c_double, c_double, c_double, c_void_p, c_void_p],
     "vqx_radam_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p],
+    "vqx_gst_workspace": [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, ctypes.POINTER(c_int64)],
+    "vqx_gst_fwd": [ctypes.POINTER(GstArgs), c_void_p],
+    "vqx_gst_bwd": [ctypes.POINTER(GstArgs), c_void_p],
 }
 EXPORTS = tuple(_SIGS) + ("vqx_last_error", "vqx_version")
 

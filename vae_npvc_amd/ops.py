@@ -910,6 +910,75 @@ def vq_plain_bwd(z, z_norm, z_len, zq, dzq, src_t, T, normalize, beta, scale, dz
          ptr(e_len), emb.shape[0], ptr(dE), stream_ptr())
 
 
+GST_PARAMS = ("gst_embs", "wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo")  # vqx_gst_args order
+
+
+def gst_workspace(B, N, F, H, R, E):
+    """Floats of the workspace one gst_fwd + gst_bwd pair shares (vqx_gst_workspace)."""
+    out = ctypes.c_int64()
+    call("vqx_gst_workspace", int(B), int(N), int(F), int(H), int(R), int(E), ctypes.byref(out))
+    return out.value
+
+
+def _gst_args(z, T, params, heads, ws, what):
+    """The parts of vqx_gst_args both directions share.  z: f32 [B*T, >= R] rows
+    (stride(0) = ldz); params: the nine f32 tensors in GST_PARAMS order."""
+    _check_cuda(z, ws, *params)
+    emb, wq, bq, wk, bk, wv, bv, wo, bo = params
+    for t in (z, ws, *params):
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: f32 tensors only")
+    if z.dim() != 2 or z.stride(1) != 1 or z.shape[0] % T or not all(p.is_contiguous() for p in params):
+        raise ValueError(f"{what}: z must be [B*T, R] rows with unit column stride, the parameters contiguous")
+    (N, E), (F, R) = emb.shape, wq.shape
+    if tuple(wk.shape) != (F, E) or tuple(wv.shape) != (F, E) or tuple(wo.shape) != (F, F) \
+            or any(tuple(b.shape) != (F,) for b in (bq, bk, bv, bo)) or z.shape[1] != R:
+        raise ValueError(f"{what}: parameter shapes do not fit gst_embs {tuple(emb.shape)} / wq {tuple(wq.shape)}")
+    a = L.GstArgs()
+    a.z, a.ws = ptr(z), ptr(ws)
+    for name, p in zip(GST_PARAMS, params):
+        setattr(a, name, ptr(p))
+    a.B, a.T, a.R, a.N, a.E, a.F, a.H, a.ldz = z.shape[0] // T, T, R, N, E, F, heads, z.stride(0)
+    need = gst_workspace(a.B, N, F, heads, R, E)
+    if ws.numel() < need or not ws.is_contiguous():
+        raise ValueError(f"{what}: workspace {ws.numel()} < {need} floats")
+    _rows(z, z.shape[0], a.ldz, R, f"{what} z")
+    return a
+
+
+def gst_fwd(z, T, params, heads, style, ws):
+    """style [B, F] = the style-token layer of mean_t z (vqx_gst_fwd, 2 launches);
+    `ws` (gst_workspace floats) keeps what gst_bwd reads."""
+    a = _gst_args(z, T, params, heads, ws, "gst_fwd")
+    _check_cuda(style)
+    if tuple(style.shape) != (a.B, a.F) or not style.is_contiguous() or style.dtype != torch.float32:
+        raise ValueError(f"gst_fwd: style must be a contiguous f32 [{a.B}, {a.F}]")
+    a.style = ptr(style)
+    call("vqx_gst_fwd", ctypes.byref(a), stream_ptr())
+    return style
+
+
+def gst_bwd(z, T, params, heads, d_style, ws, dz, grads):
+    """From d_style [B, F] and the `ws` gst_fwd filled (vqx_gst_bwd, 3 launches):
+    dz [B*T, >= R] rows and `grads`, nine tensors shaped like `params`; all overwritten."""
+    a = _gst_args(z, T, params, heads, ws, "gst_bwd")
+    _check_cuda(d_style, dz, *grads)
+    if tuple(d_style.shape) != (a.B, a.F) or not d_style.is_contiguous() or d_style.dtype != torch.float32:
+        raise ValueError(f"gst_bwd: d_style must be a contiguous f32 [{a.B}, {a.F}]")
+    if dz.dim() != 2 or dz.shape[0] != z.shape[0] or dz.shape[1] != a.R or dz.stride(1) != 1 \
+            or dz.dtype != torch.float32:
+        raise ValueError(f"gst_bwd: dz must be f32 [{z.shape[0]}, {a.R}] rows with unit column stride")
+    if len(grads) != len(params) or any(g.shape != p.shape or not g.is_contiguous() or g.dtype != torch.float32
+                                        for g, p in zip(grads, params)):
+        raise ValueError("gst_bwd: grads must be contiguous f32 tensors shaped like the parameters")
+    a.d_style, a.dz, a.lddz = ptr(d_style), ptr(dz), dz.stride(0)
+    for name, g in zip(GST_PARAMS, grads):
+        setattr(a, "d_gst_embs" if name == "gst_embs" else "d" + name, ptr(g))
+    _rows(dz, dz.shape[0], a.lddz, a.R, "gst_bwd dz")
+    call("vqx_gst_bwd", ctypes.byref(a), stream_ptr())
+    return dz
+
+
 def cu_masked_stream(reserve_cus):
     """A torch ExternalStream on all but `reserve_cus` CUs of the current
     device (vqx_stream_create_cu_mask) and the CU count it may use; release it
