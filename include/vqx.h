@@ -43,7 +43,11 @@ enum {
 /* epilogue flags of vqx_conv1d_fwd / vqx_conv1d_dgrad, applied in this order */
 enum {
   VQX_EPI_BIAS = 1 << 0,    /* v += bias[c]                                    */
-  VQX_EPI_ROWBIAS = 1 << 1, /* v += rowbias[(n/T)*cout + c]  (conv_cond term)  */
+  VQX_EPI_ROWBIAS = 1 << 1, /* v += rowbias[(n/T)*cout + c]  (conv_cond term); with
+                               rowbias_T = Tc > 1 (forward only, ABI 130) the term
+                               varies in time: rowbias is [B*Tc][cout] and frame
+                               t = n - b*T of utterance b = n/T reads row
+                               b*Tc + min(t / (T/Tc), Tc - 1)                   */
   VQX_EPI_MASK = 1 << 2,    /* v *= (mask[n][c] > 0 ? 1 : mask_slope)*mask_scale */
   VQX_EPI_RES = 1 << 3,     /* v += res[n][c]                                  */
   VQX_EPI_GNADD = 1 << 4,   /* v += (gn_h[n][c]-mean[b])*rstd[b]*gamma[c]+beta[c] */
@@ -88,7 +92,7 @@ typedef struct vqx_conv_args {
   const void* w;             /* packed weight [cout_fwd][ntaps*cin_fwd]        */
   void* y;                   /* [N][ldy]                                       */
   const float* bias;         /* [cout]                                         */
-  const float* rowbias;      /* [B][cout]                                      */
+  const float* rowbias;      /* [B][cout], or [B*rowbias_T][cout]              */
   const void* res;           /* [N][ldres]  dtype                              */
   const void* mask;          /* [N][ldmask] dtype                              */
   const void* gn_h;          /* [N][ldgn]   dtype                              */
@@ -122,6 +126,11 @@ typedef struct vqx_conv_args {
                                 layer's ntaps/dil and pad' = (ntaps-1)*dil - pad    */
   int32_t kernel_policy;     /* VQX_POLICY_* (ABI 122): which bf16 GEMM kernels this call may
                                 use; 0 = automatic.  Per call, no process-wide state.         */
+  int32_t rowbias_T;         /* ABI 130: rows of rowbias per utterance (Tc); 0 or 1 = one row per
+                                utterance.  Tc > 1: forward only, Tc <= T, T * (T / Tc) < 2^32
+                                (dgrad and dgrad_wgrad return -1); the conv_cond term of a
+                                conditioning stretched from Tc to T frames (vqvae2.py:105-114),
+                                see VQX_EPI_ROWBIAS                                            */
 } vqx_conv_args;
 
 /* Kernel policy of a conv GEMM call (vqx_conv_args / vqx_wgrad_args
@@ -756,8 +765,38 @@ int vqx_gst_workspace(int32_t B, int32_t N, int32_t F, int32_t H, int32_t R, int
 int vqx_gst_fwd(const vqx_gst_args* a, vqx_stream_t stream);
 int vqx_gst_bwd(const vqx_gst_args* a, vqx_stream_t stream);
 
+/*
+ * Level upsampling + concatenation of the hierarchical decoders (ABI 130;
+ * Model.upsample + torch.cat, vqvae2.py:105-114, 130-143).  A level l is
+ * frame-major fp32 z_l [B][T_l][ld] with C_l channels and 1 <= T_l <= T;
+ * stretched to T frames, frame t reads src_l(t) = min(t / (T / T_l), T_l - 1)
+ * (repetition by T / T_l, the tail replicate-padded; nothing is cropped).
+ *   fwd: out[b*T + t][off_l + c] = z_l[b][src_l(t)][c], off_l the running sum
+ *        of C_l; out [B*T][ldo] in VQX_F32 (a copy) or VQX_BF16 (rounded to
+ *        nearest even); columns from sum C_l up are not written.
+ *   bwd: z_l (overwritten) = dz_l[b][s][c] = sum_{t: src_l(t) = s}
+ *        dout[b*T + t][off_l + c], dout fp32 or bf16, accumulated in fp32 in a
+ *        fixed order without atomics (vqx_hier.hip states it): equal shapes
+ *        give equal bits.  With one level of all the columns it is the
+ *        per-segment column sum (the gradient of a segmented row bias).
+ * Up to 8 levels, passed by value to the kernels (no device table).  Limits
+ * (else -1): n_levels in 1..8; dtype F32 | BF16; B, T >= 1, B*T < 2^31;
+ * every pointer non-NULL and 16-B aligned; C_l, ld_l, ldo multiples of 4,
+ * ld_l >= C_l; sum C_l <= ldo.
+ */
+typedef struct vqx_hier_level {
+  void* z;               /* fwd: source (read); bwd: dz (written)  [B][T_l][ld] f32 */
+  int32_t T_l, C, ld;
+} vqx_hier_level;
+int vqx_upsample_cat_fwd(const vqx_hier_level* levels, int32_t n_levels, int32_t B, int32_t T, void* out,
+                         int32_t ldo, int32_t out_dtype, vqx_stream_t stream);
+int vqx_upsample_cat_bwd(const vqx_hier_level* levels, int32_t n_levels, int32_t B, int32_t T, const void* dout,
+                         int32_t ldo, int32_t dout_dtype, vqx_stream_t stream);
+
+/* ABI 130: vqx_conv_args.rowbias_T appended (segmented row bias of the forward
+ * epilogue; 0 or 1 keeps every earlier call's bits) and vqx_upsample_cat_*. */
 /* ABI version (major*100 + minor); VQX_ABI_VERSION is what this header describes. */
-#define VQX_ABI_VERSION 129
+#define VQX_ABI_VERSION 130
 int vqx_version(void);
 
 #ifdef __cplusplus

@@ -15,7 +15,7 @@ from pathlib import Path
 import torch  # noqa: F401  (loads the HIP runtime first; see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libvqx.so"
-ABI_VERSION = 129  # include/vqx.h VQX_ABI_VERSION
+ABI_VERSION = 130  # include/vqx.h VQX_ABI_VERSION
 
 VQX_F32, VQX_BF16 = 0, 1
 PRO_NONE, PRO_LRELU, PRO_RELU, PRO_SCALE_RELU = 0, 1, 2, 3
@@ -40,6 +40,7 @@ class ConvArgs(ctypes.Structure):
         ("y2", c_void_p), ("ldy2", c_int32), ("epi_act", c_int32), ("colsum_part", c_void_p),
         ("stat_part", c_void_p), ("gn_groups", c_int32), ("gn_glu", c_int32),
         ("gn_stat_tiles", c_void_p), ("gn_eps", c_float), ("dil", c_int32), ("kernel_policy", c_int32),
+        ("rowbias_T", c_int32),
     ]
 
 
@@ -84,6 +85,10 @@ class GstArgs(ctypes.Structure):  # include/vqx.h vqx_gst_args
         ("B", c_int32), ("T", c_int32), ("R", c_int32), ("N", c_int32), ("E", c_int32), ("F", c_int32),
         ("H", c_int32), ("ldz", c_int32), ("lddz", c_int32),
     ]
+
+
+class HierLevel(ctypes.Structure):  # include/vqx.h vqx_hier_level
+    _fields_ = [("z", c_void_p), ("T_l", c_int32), ("C", c_int32), ("ld", c_int32)]
 
 
 WN_COLREDUCE = 2
@@ -190,6 +195,10 @@ _SIGS = {
     "vqx_gst_workspace": [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, ctypes.POINTER(c_int64)],
     "vqx_gst_fwd": [ctypes.POINTER(GstArgs), c_void_p],
     "vqx_gst_bwd": [ctypes.POINTER(GstArgs), c_void_p],
+    "vqx_upsample_cat_fwd": [ctypes.POINTER(HierLevel), c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                             c_void_p],
+    "vqx_upsample_cat_bwd": [ctypes.POINTER(HierLevel), c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                             c_void_p],
 }
 EXPORTS = tuple(_SIGS) + ("vqx_last_error", "vqx_version")
 

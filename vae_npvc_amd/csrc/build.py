@@ -18,7 +18,7 @@ OUT_DIR = PKG / "lib"
 LIB = OUT_DIR / "libvqx.so"
 SOURCES = ["vqx_runtime.hip", "vqx_gemm.hip", "vqx_gemm_fwd.hip", "vqx_gemm_dgrad.hip", "vqx_gemm_wgrad.hip",
            "vqx_gemm_dual.hip",
-           "vqx_vq.hip", "vqx_misc.hip", "vqx_gst.hip"]
+           "vqx_vq.hip", "vqx_misc.hip", "vqx_gst.hip", "vqx_hier.hip"]
 HEADERS = ["vqx_common.h", "vqx_gemm_kernel.h", "vqx_gemm_inst.h", "vqx_gemm_pp.h", "vqx_gn_math.h",
            str(ROOT / "include" / "vqx.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -109,6 +109,10 @@ static int conv_prepare(const vqx_conv_args* a, int mode, GemmParams& P, bool& g
   const int epi = a->epilogue;
   if ((epi & VQX_EPI_BIAS) && (!a->bias || !aligned16(a->bias))) { set_error("vqx_conv: BIAS needs a 16-B aligned bias"); return -1; }
   if ((epi & VQX_EPI_ROWBIAS) && (!a->rowbias || !aligned16(a->rowbias))) { set_error("vqx_conv: ROWBIAS needs an aligned rowbias"); return -1; }
+  if (a->rowbias_T > 1) {  // segmented row bias (ABI 130): [B*Tc][cout], forward only
+    if (mode != MODE_FWD) { set_error("vqx_conv: rowbias_T %d > 1 is a forward epilogue (not on dgrad)", a->rowbias_T); return -1; }
+    if (!(epi & VQX_EPI_ROWBIAS) || a->rowbias_T > a->T) { set_error("vqx_conv: rowbias_T %d needs ROWBIAS and rowbias_T <= T %d", a->rowbias_T, a->T); return -1; }
+  } else if (a->rowbias_T < 0) { set_error("vqx_conv: rowbias_T %d < 0", a->rowbias_T); return -1; }
   if ((epi & VQX_EPI_RES) && (!a->res || a->ldres % 8 || !aligned16(a->res))) { set_error("vqx_conv: RES operand"); return -1; }
   if ((epi & VQX_EPI_MASK) && (!a->mask || a->ldmask % 8 || !aligned16(a->mask))) { set_error("vqx_conv: MASK operand"); return -1; }
   if ((epi & VQX_EPI_GNADD) && !(a->gn_h && a->gn_mean_rstd && a->gn_gamma && a->gn_beta && a->ldgn % 8 == 0 && aligned16(a->gn_h) && aligned16(a->gn_gamma) && aligned16(a->gn_beta))) { set_error("vqx_conv: GNADD operands"); return -1; }
@@ -150,6 +154,12 @@ static int conv_prepare(const vqx_conv_args* a, int mode, GemmParams& P, bool& g
   P.stat_part = a->stat_part; P.gn_groups = a->gn_groups; P.gn_glu = a->gn_glu;
   P.gn_tiles = a->gn_stat_tiles; P.gn_eps = a->gn_eps;
   P.policy = a->kernel_policy;
+  if (a->rowbias_T > 1) {
+    const unsigned d = (unsigned)(a->T / a->rowbias_T);
+    if ((uint64_t)a->T * d >= (1ull << 32)) { set_error("vqx_conv: rowbias_T: T %d * (T / rowbias_T) must be below 2^32", a->T); return -1; }
+    P.rb_T = a->rowbias_T;
+    P.rb_magic = d >= 2 ? (unsigned)((1ull << 32) / d) + 1u : 0u;
+  }
   if (P.gn_tiles && (mode != MODE_FWD || !(epi & VQX_EPI_GNADD) || a->T % 128 || a->cout % 128 ||
                      a->gn_groups != 1 || !a->gn_mean_rstd)) {
     set_error("vqx_conv: gn_stat_tiles needs FWD with GNADD, G = 1, T %% 128 == 0, cout %% 128 == 0 and gn_mean_rstd");

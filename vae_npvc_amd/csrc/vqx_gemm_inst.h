@@ -90,7 +90,10 @@ void launch_tr(const GemmParams& P, int grid, hipStream_t s) {
       return;
     }
   }
-  if (const int segs = tr8_segs(P)) {
+  if (int segs = tr8_segs(P)) {
+    // the ping-pong kernel's generic-epilogue instance (at the register limit)
+    // is built without the segmented row bias: such a call takes 256-frame tiles
+    if (segs == 2 && EK == EK_ALL && P.rb_T) segs = 1;
     GemmParams Q = P;
     Q.tiles_m = (int)(P.n_rows / (256 * segs));
     if (segs == 2) {  // gen = 6: conv_pp_kernel (ping-pong groups), prologue slot = SEGS

@@ -96,6 +96,12 @@ struct GemmParams {
   int policy;      // host side: the call's kernel_policy (vqx_conv_args / vqx_wgrad_args)
   float* fix_dw;           // WGRAD (tap reuse, bf16 slabs): in-launch split-K reduction target, or null
   unsigned* fix_cnt;       // ... its per-tile arrival counters (left zero)
+  // FWD segmented ROWBIAS (vqx_conv_args.rowbias_T > 1): rows per utterance
+  // (0: one) and t / (T / rb_T) as umulhi(t, rb_magic), exact for t < T
+  // (rb_magic = floor(2^32 / d) + 1 for d = T / rb_T >= 2, host-checked
+  // T * d < 2^32; d = 1: rb_magic 0 and the quotient is t)
+  int rb_T;
+  unsigned rb_magic;
 };
 
 template <typename T> struct Cfg;
@@ -383,7 +389,7 @@ __device__ __forceinline__ void row_op(const EpiOps& o, int role, const void* ba
 // order bias, row bias, activation-derivative mask, split to out2 (returns),
 // residual, GroupNorm-apply add, activation, store.  `o`: prefetched row
 // operands (none: k0 = k1 = EPR_NONE).
-template <typename T, int EMASK, bool PRE = false>
+template <typename T, int EMASK, bool PRE = false, bool SEG = false>
 __device__ __forceinline__ void epilogue8(const GemmParams& P, int64_t row, int col, float* v, const float* gmr,
                                           const EpiOps& o, const EpiVec& V) {
   const int epi = P.epi & EMASK;
@@ -395,7 +401,18 @@ __device__ __forceinline__ void epilogue8(const GemmParams& P, int64_t row, int 
     for (int e = 0; e < 8; ++e) v[e] += t[e];
   }
   if (epi & VQX_EPI_ROWBIAS) {
-    ld8<float>(P.rowbias, (int64_t)bidx * P.Nc + col, t);
+    int ridx = bidx;
+    if constexpr (SEG) {
+      // segmented: row b*Tc + min(t / (T / Tc), Tc - 1), the stretched conditioning's source frame.
+      // Marked unlikely so the block sits out of line: the one-row-per-utterance
+      // calls of the training step fall through a not-taken scalar branch
+      if (__builtin_expect(P.rb_T != 0, 0)) {
+        const unsigned t_in = (unsigned)((int)row - bidx * P.T);
+        const int seg = (int)(P.rb_magic ? __umulhi(t_in, P.rb_magic) : t_in);
+        ridx = bidx * P.rb_T + (seg < P.rb_T ? seg : P.rb_T - 1);
+      }
+    }
+    ld8<float>(P.rowbias, (int64_t)ridx * P.Nc + col, t);
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] += t[e];
   }
@@ -563,7 +580,7 @@ __device__ __forceinline__ void wait_vm(int n) {
 // 44 KiB of `smem`; the caller's staging buffers must be free.  `tid` is the
 // thread's index in the 4-wave group that owns the tile (conv_tr8_kernel runs
 // two such groups side by side; every group passes the same barriers).
-template <typename T, int MODE, int EK, bool PRE = false, bool PREVEC = PRE>
+template <typename T, int MODE, int EK, bool PRE = false, bool PREVEC = PRE, bool SEGOK = true>
 __device__ __forceinline__ void tile_epilogue(const GemmParams& P, f32x16_t (&acc)[2][2], char* smem, int m0, int n0,
                                               int tn, int split, const float* gmr, int tid,
                                               const EpiRows* R = nullptr) {
@@ -621,7 +638,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& P, f32x16_t (&ac
       } else {
         if (row < P.n_rows && col < P.Nc) {
           const EpiOps o = epi_ops<slab * 4 + pass, PRE>(R);
-          epilogue8<T, EMASK, PREVEC>(P, row, col, v, gmr, o, V);
+          epilogue8<T, EMASK, PREVEC, MODE == MODE_FWD && SEGOK>(P, row, col, v, gmr, o, V);
 #pragma unroll
           for (int e = 0; e < 8; ++e) cs[e] += v[e];
           if (P.epi & EMASK & VQX_EPI_GNSTATS) {  // two-pass moments of the 8 values, merged

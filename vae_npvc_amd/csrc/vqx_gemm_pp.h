@@ -251,7 +251,7 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(GemmParams P) {
   }
 #pragma unroll
   for (int j = 0; j < SEGS; ++j)
-    tile_epilogue<T, MODE, EK>(P, acc[j], smem + grp * EPI_BYTES, (int)(m0 + (grp * SEGS + j) * 128), n0, tn, 0,
+    tile_epilogue<T, MODE, EK, false, false, EK != EK_ALL>(P, acc[j], smem + grp * EPI_BYTES, (int)(m0 + (grp * SEGS + j) * 128), n0, tn, 0,
                                P.gn_mr, tid & 255);
 }
 

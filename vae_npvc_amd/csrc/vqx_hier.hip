@@ -1,0 +1,231 @@
+// Level upsampling + channel concatenation of the hierarchical decoders
+// (include/vqx.h vqx_upsample_cat_*; reference vqvae2.py:105-114 `upsample`,
+// 130-143 the torch.cat of the stretched levels) and its adjoint.
+//
+// A level l is frame-major fp32 [B][T_l][C_l]; stretched to T frames, frame t
+// reads source frame src_l(t) = min(t / (T / T_l), T_l - 1): repetition by
+// T / T_l, the tail replicate-padded from the last frame.
+//   forward   hier_cat_fwd_kernel  one thread per (output row, V channels):
+//             out[b*T + t][off_l + c] = z_l[b][src_l(t)][c], converted to the
+//             destination type.  Pure copy: V = 8 (two 16-B loads, 16-B or
+//             2 x 16-B stores) when every width and offset allows, else V = 4.
+//   backward  hier_cat_bwd_kernel  one (level, b, s, 4 channels) item per
+//             thread column: dz_l[b][s][c] = sum of dout[b*T + t][off_l + c]
+//             over the frames t of segment s.
+// Summation order of the backward (fixed, no atomics): the segment's frames
+// t0 .. t1-1 are cut into P contiguous chunks of ceil((t1 - t0) / P) frames;
+// each chunk is added in ascending t starting from 0.f, and the chunk sums are
+// added in ascending chunk order starting from 0.f.  P = 1 when the longest
+// segment of the call (the tail segment T - (T_l - 1) * (T / T_l) of some
+// level) is below 32 frames, else 8; it depends on the shapes alone, so two
+// calls with the same shapes give the same bits.
+#include "vqx_common.h"
+
+namespace vqx {
+namespace {
+
+constexpr int HIER_MAX_LEVELS = 8;
+constexpr int HIER_THREADS = 256;
+constexpr int HIER_BWD_LANES = 64;   // items per workgroup of the backward
+constexpr int HIER_BWD_PARTS = 8;    // chunks per long segment
+constexpr int HIER_LONG_SEG = 32;    // segments from this length up are cut into chunks
+
+// Passed by value (as vqx_gather_rows_host passes its rows): no device table.
+struct HierLevels {
+  float* z[HIER_MAX_LEVELS];       // fwd: source; bwd: destination
+  int64_t start[HIER_MAX_LEVELS];  // bwd: first item of the level
+  int T_l[HIER_MAX_LEVELS], rep[HIER_MAX_LEVELS], ld[HIER_MAX_LEVELS];
+  int g0[HIER_MAX_LEVELS];         // first granule (V channels) of the level in an output row
+  int off[HIER_MAX_LEVELS];        // first output column of the level
+  int n;
+};
+
+struct HierPick {
+  float* z;
+  int64_t start;
+  int T_l, rep, ld, g0, off;
+};
+
+// Level of granule g (fwd) or item i (bwd): the last level whose start is not
+// above it.  Unrolled selects on uniform loads, no divergent table index.
+template <bool BY_ITEM>
+__device__ __forceinline__ HierPick hier_pick(const HierLevels& L, int64_t key) {
+  HierPick p = {L.z[0], L.start[0], L.T_l[0], L.rep[0], L.ld[0], L.g0[0], L.off[0]};
+#pragma unroll
+  for (int l = 1; l < HIER_MAX_LEVELS; ++l) {
+    const bool take = l < L.n && key >= (BY_ITEM ? L.start[l] : (int64_t)L.g0[l]);
+    if (take) p = {L.z[l], L.start[l], L.T_l[l], L.rep[l], L.ld[l], L.g0[l], L.off[l]};
+  }
+  return p;
+}
+
+template <int V, bool BF16>
+__global__ __launch_bounds__(HIER_THREADS) void hier_cat_fwd_kernel(HierLevels L, int64_t rows, int T, int gran,
+                                                                     void* __restrict__ out, int64_t ldo) {
+  const int64_t i = (int64_t)blockIdx.x * HIER_THREADS + threadIdx.x;
+  if (i >= rows * gran) return;
+  const int64_t row = i / gran;
+  const int g = (int)(i - row * gran);
+  const HierPick p = hier_pick<false>(L, g);
+  const int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
+  int s = t / p.rep;
+  s = s < p.T_l ? s : p.T_l - 1;
+  const int c = (g - p.g0) * V;
+  const float* src = p.z + ((int64_t)b * p.T_l + s) * p.ld + c;
+  const int64_t at = row * ldo + p.off + c;
+  float v[V];
+#pragma unroll
+  for (int q = 0; q < V / 4; ++q) {
+    const f32x4_t x = *(const f32x4_t*)(src + 4 * q);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[4 * q + e] = x[e];
+  }
+  if constexpr (BF16) {
+    unsigned w[V / 2];
+#pragma unroll
+    for (int e = 0; e < V / 2; ++e) w[e] = pack_bf16x2(v[2 * e], v[2 * e + 1]);
+    bf16_t* dst = (bf16_t*)out + at;
+    if constexpr (V == 8) *(uint4*)dst = make_uint4(w[0], w[1], w[2], w[3]);
+    else *(uint2*)dst = make_uint2(w[0], w[1]);
+  } else {
+    float* dst = (float*)out + at;
+#pragma unroll
+    for (int q = 0; q < V / 4; ++q) {
+      const f32x4_t x = {v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
+      *(f32x4_t*)(dst + 4 * q) = x;
+    }
+  }
+}
+
+// blockDim = (HIER_BWD_LANES, P): lane x owns one item, chunk y of its segment.
+template <bool BF16>
+__global__ __launch_bounds__(HIER_BWD_LANES* HIER_BWD_PARTS) void hier_cat_bwd_kernel(HierLevels L, int64_t items, int T,
+                                                                                      const void* __restrict__ dout,
+                                                                                      int64_t ldo) {
+  __shared__ f32x4_t part[HIER_BWD_PARTS][HIER_BWD_LANES];
+  const int64_t i = (int64_t)blockIdx.x * HIER_BWD_LANES + threadIdx.x;
+  const int P = blockDim.y, y = threadIdx.y;
+  const bool live = i < items;
+  HierPick p = hier_pick<true>(L, live ? i : 0);
+  f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+  int64_t dst = 0;
+  if (live) {  // items of a level are ordered (b, s, granule of 4 channels)
+    const int gl = p.g0;  // the backward table's g0 is the level's granule count C_l / 4
+    const int64_t j = i - p.start;
+    const int g = (int)(j % gl);
+    const int64_t bs = j / gl;
+    const int s = (int)(bs % p.T_l);
+    const int64_t b = bs / p.T_l;
+    const int t0 = s * p.rep, t1 = s == p.T_l - 1 ? T : t0 + p.rep;
+    const int len = t1 - t0, chunk = (len + P - 1) / P;
+    const int a0 = t0 + y * chunk, a1 = a0 + chunk < t1 ? a0 + chunk : t1;
+    const int64_t col = p.off + 4 * g;
+    for (int t = a0; t < a1; ++t) {
+      const int64_t at = (b * T + t) * ldo + col;
+      if constexpr (BF16) {
+        const uint2 w = *(const uint2*)((const bf16_t*)dout + at);
+        acc[0] += __uint_as_float(w.x << 16);
+        acc[1] += __uint_as_float(w.x & 0xffff0000u);
+        acc[2] += __uint_as_float(w.y << 16);
+        acc[3] += __uint_as_float(w.y & 0xffff0000u);
+      } else {
+        const f32x4_t x = *(const f32x4_t*)((const float*)dout + at);
+        acc += x;
+      }
+    }
+    dst = (b * p.T_l + s) * p.ld + 4 * g;
+  }
+  if (P == 1) {
+    if (live) *(f32x4_t*)(p.z + dst) = acc;
+    return;
+  }
+  part[y][threadIdx.x] = acc;
+  __syncthreads();
+  if (y == 0 && live) {
+    f32x4_t sum = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < P; ++k) sum += part[k][threadIdx.x];
+    *(f32x4_t*)(p.z + dst) = sum;
+  }
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// Checks shared by both directions; fills the by-value table.  `v8` = every
+// width, offset and stride allows 8-channel granules.
+int hier_prepare(const char* who, const vqx_hier_level* lv, int n, int B, int T, const void* out, int ldo, int dtype,
+                 HierLevels& L, int& total, bool& v8, int& longest) {
+  if (!lv) { set_error("%s: null levels", who); return -1; }
+  if (n < 1 || n > HIER_MAX_LEVELS) { set_error("%s: n_levels = %d not in 1..%d", who, n, HIER_MAX_LEVELS); return -1; }
+  if (dtype != VQX_F32 && dtype != VQX_BF16) { set_error("%s: bad dtype %d", who, dtype); return -1; }
+  if (B < 1 || T < 1 || (int64_t)B * T > INT32_MAX) { set_error("%s: B = %d, T = %d (B*T must fit 31 bits)", who, B, T); return -1; }
+  if (!out || !aligned16(out)) { set_error("%s: null or unaligned (16 B) full-rate pointer", who); return -1; }
+  L = HierLevels{};
+  L.n = n;
+  total = 0;
+  longest = 1;
+  v8 = ldo % 8 == 0;
+  for (int l = 0; l < n; ++l) {
+    const vqx_hier_level& v = lv[l];
+    if (!v.z || !aligned16(v.z)) { set_error("%s: level %d: null or unaligned (16 B) pointer", who, l); return -1; }
+    if (v.T_l < 1 || v.T_l > T) { set_error("%s: level %d: T_l = %d not in 1..T = %d", who, l, v.T_l, T); return -1; }
+    if (v.C < 4 || v.C % 4 || v.ld % 4 || v.ld < v.C) { set_error("%s: level %d: C = %d / ld = %d must be multiples of 4, ld >= C", who, l, v.C, v.ld); return -1; }
+    L.z[l] = (float*)v.z;
+    L.T_l[l] = v.T_l;
+    L.rep[l] = T / v.T_l;
+    L.ld[l] = v.ld;
+    L.off[l] = total;
+    if (v.C % 8) v8 = false;
+    const int last = T - (v.T_l - 1) * (T / v.T_l);  // the tail segment is the longest
+    if (last > longest) longest = last;
+    if ((int64_t)total + v.C > INT32_MAX) { set_error("%s: channel sum overflows", who); return -1; }
+    total += v.C;
+  }
+  if (ldo % 4 || total > ldo) { set_error("%s: sum of C_l = %d exceeds ldo = %d (ldo a multiple of 4)", who, total, ldo); return -1; }
+  return 0;
+}
+
+}  // namespace
+}  // namespace vqx
+
+using namespace vqx;
+
+extern "C" int vqx_upsample_cat_fwd(const vqx_hier_level* levels, int32_t n_levels, int32_t B, int32_t T, void* out,
+                                    int32_t ldo, int32_t out_dtype, vqx_stream_t stream) {
+  HierLevels L;
+  int total, longest;
+  bool v8;
+  if (hier_prepare("vqx_upsample_cat_fwd", levels, n_levels, B, T, out, ldo, out_dtype, L, total, v8, longest)) return -1;
+  const int V = v8 ? 8 : 4;
+  for (int l = 0; l < n_levels; ++l) L.g0[l] = L.off[l] / V;
+  const int gran = total / V;
+  const int64_t rows = (int64_t)B * T, threads = rows * gran;
+  const int64_t grid = (threads + HIER_THREADS - 1) / HIER_THREADS;
+  if (grid > INT32_MAX) { set_error("vqx_upsample_cat_fwd: %lld workgroups", (long long)grid); return -1; }
+  hipStream_t s = (hipStream_t)stream;
+  const bool bf = out_dtype == VQX_BF16;
+  auto* fn = v8 ? (bf ? hier_cat_fwd_kernel<8, true> : hier_cat_fwd_kernel<8, false>)
+                : (bf ? hier_cat_fwd_kernel<4, true> : hier_cat_fwd_kernel<4, false>);
+  hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(HIER_THREADS), 0, s, L, rows, T, gran, out, (int64_t)ldo);
+  return launch_status("vqx_upsample_cat_fwd");
+}
+
+extern "C" int vqx_upsample_cat_bwd(const vqx_hier_level* levels, int32_t n_levels, int32_t B, int32_t T,
+                                    const void* dout, int32_t ldo, int32_t dout_dtype, vqx_stream_t stream) {
+  HierLevels L;
+  int total, longest;
+  bool v8;
+  if (hier_prepare("vqx_upsample_cat_bwd", levels, n_levels, B, T, dout, ldo, dout_dtype, L, total, v8, longest)) return -1;
+  int64_t items = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    L.start[l] = items;
+    L.g0[l] = levels[l].C / 4;  // granules per source frame
+    items += (int64_t)B * L.T_l[l] * L.g0[l];
+  }
+  const int64_t grid = (items + HIER_BWD_LANES - 1) / HIER_BWD_LANES;
+  if (grid > INT32_MAX) { set_error("vqx_upsample_cat_bwd: %lld workgroups", (long long)grid); return -1; }
+  const int P = longest >= HIER_LONG_SEG ? HIER_BWD_PARTS : 1;
+  hipStream_t s = (hipStream_t)stream;
+  auto* fn = dout_dtype == VQX_BF16 ? hier_cat_bwd_kernel<true> : hier_cat_bwd_kernel<false>;
+  hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(HIER_BWD_LANES, P), 0, s, L, items, T, dout, (int64_t)ldo);
+  return launch_status("vqx_upsample_cat_bwd");
+}

@@ -1,0 +1,413 @@
+"""Building blocks of the hierarchical model (reference model/vqvae2.py, recipe
+egs/vcc20/vae2) on the MI355X: level upsampling (`Model.upsample`,
+vqvae2.py:130-143), its concatenation (vqvae2.py:105-114) and the decoder
+with conditioning that varies in time (`Decoder`, vqvae2.py:274-371).
+
+`Decoder` has the reference's constructor arguments, module tree, parameter
+order and state_dict keys (those of `model.vqvae.Decoder`, which it extends)
+plus `compute_dtype: fp32|bf16`.  `forward((x, c))` takes the reference's
+full-rate conditioning tensor `c` (B, cond, T) or a list of levels
+(B, C_l, T_l) that stands for `cat([upsample(l, T)])`.
+
+Every ResSkip block adds conv_cond(c) before its GroupNorm (layers.py:229-236).
+conv_cond is 1x1, so it commutes with the stretching: the term is computed at
+the conditioning's own rate Tc (B*Tc rows) and added in the conv_in GEMM's
+epilogue by segment (vqx_conv_args.rowbias_T); neither the stretched `c` nor
+conv_cond(c) exists at full rate, forward or backward.
+
+The forward and backward are the launch sequences of engine/step.py
+decoder_fwd / decoder_bwd composed from `ops.*` calls inside one
+torch.autograd.Function.  Weight norm goes through torch autograd on
+`effective_weight()`: the function receives w = g*v/||v|| in torch's layout,
+packs it for the GEMMs and returns dL/dw in the same layout.  The conditioning
+GEMMs (conv_cond and its gradients) run in fp32 in both compute dtypes, as the
+engine's speaker conditioning does.  There is no CPU path.
+"""
+import functools
+import math
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from .. import _lib as L
+from .. import ops
+from .layers import ResSkipBlock, WNConv1d
+from .vqvae import Decoder as _Decoder
+
+F32 = torch.float32
+_DT = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
+# ------------------------------------------------------------------ host logic
+def src_index(target_len, level_len):
+    """Source frame of every output frame of `upsample` (vqvae2.py:130-143):
+    repetition by target_len // level_len, the tail replicate-padded."""
+    if not 1 <= level_len <= target_len:
+        raise ValueError(f"upsample: level length {level_len} not in 1..{target_len}")
+    r = target_len // level_len
+    return [min(t // r, level_len - 1) for t in range(target_len)]
+
+
+@functools.lru_cache(maxsize=256)
+def choose_tc(T, level_lens):
+    """Rate Tc of the conditioning term for levels of lengths `level_lens`
+    stretched to T: max T_l when stretching every level to Tc and then to T
+    lands on the frames of the direct stretch, else T (full rate)."""
+    level_lens = tuple(level_lens)
+    Tc = max(level_lens)
+    if Tc == T:
+        return T
+    outer = src_index(T, Tc)
+    for Tl in level_lens:
+        inner, direct = src_index(Tc, Tl), src_index(T, Tl)
+        if any(inner[outer[t]] != direct[t] for t in range(T)):
+            return T
+    return Tc
+
+
+def _to_rows(z):
+    """(B, C, T) -> frame-major f32 [B*T, C]."""
+    B, C, T = z.shape
+    y = torch.empty(B * T, C, device=z.device, dtype=F32)
+    ops.nct_to_ntc(z.float().contiguous(), y)
+    return y
+
+
+def _to_nct(y, B, T):
+    x = torch.empty(B, y.shape[1], T, device=y.device, dtype=F32)
+    ops.ntc_to_nct(y, x)
+    return x
+
+
+class _UpsampleCatFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, target_len, *levels):
+        if not all(z.is_cuda for z in levels):
+            raise L.VqxError("upsample_cat runs on the MI355X only (libvqx); move the levels with .cuda()")
+        B = levels[0].shape[0]
+        rows = [_to_rows(z) for z in levels]
+        out = torch.empty(B * target_len, sum(r.shape[1] for r in rows), device=levels[0].device, dtype=F32)
+        ops.upsample_cat_fwd(rows, B, target_len, out)
+        ctx.shapes, ctx.T = [tuple(z.shape) for z in levels], target_len
+        return _to_nct(out, B, target_len)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        B, T = ctx.shapes[0][0], ctx.T
+        d = _to_rows(dout)
+        dl = [torch.empty(B * Tl, C, device=dout.device, dtype=F32) for _, C, Tl in ctx.shapes]
+        ops.upsample_cat_bwd(dl, B, T, d)
+        return (None, *[_to_nct(g, B, s[2]) for g, s in zip(dl, ctx.shapes)])
+
+
+def upsample_cat(levels, target_len):
+    """cat([upsample(l, target_len) for l in levels], dim=1) for levels (B, C_l, T_l)."""
+    levels = list(levels)
+    if not levels or any(z.dim() != 3 or z.shape[0] != levels[0].shape[0] for z in levels):
+        raise ValueError("upsample_cat: levels must be (B, C_l, T_l) tensors of one batch size")
+    for z in levels:
+        src_index(target_len, z.shape[2])
+    return _UpsampleCatFn.apply(target_len, *levels)
+
+
+def upsample(z, target_len):
+    """The reference's Model.upsample (vqvae2.py:130-143) for z (B, C, T_l), T_l <= target_len."""
+    return upsample_cat([z], target_len)
+
+
+# ------------------------------------------------------------------ decoder
+def _pack(w, transposed, dt):
+    """torch-layout effective weight -> the GEMMs' [cout, k*cin] (include/vqx.h;
+    ConvTranspose: tap j reads v[ci][co][k-1-j])."""
+    if transposed:
+        return w.flip(2).permute(1, 2, 0).reshape(w.shape[1], -1).to(dt).contiguous()
+    return w.permute(0, 2, 1).reshape(w.shape[0], -1).to(dt).contiguous()
+
+
+def _unpack_grad(slabs, transposed, k):
+    """Split-K weight-gradient slabs [splits, r, k*c] -> dL/dw in torch's layout."""
+    g = slabs.sum(0) if slabs.shape[0] > 1 else slabs[0]
+    g = g.view(g.shape[0], k, -1)
+    return (g.flip(1) if transposed else g).permute(0, 2, 1)
+
+
+class _Conv:
+    """One conv of the plan: geometry + where its tensors sit in the flat argument list."""
+
+    def __init__(self, mod, at):
+        self.transposed, self.k, self.dil = mod.transposed, mod.k, mod.dilation
+        self.cin, self.cout = mod.cin, mod.cout
+        self.pad = (mod.k - 1) * mod.dilation - mod.padding if mod.transposed else mod.padding
+        if 2 * self.pad != (mod.k - 1) * mod.dilation:
+            raise NotImplementedError("asymmetric padding (the output length would change)")
+        self.at = at  # index of w in the tensor list; bias follows
+
+
+def _wgrad(cv, dy, x, T):
+    """Slabs of dL/dw (fp32) of conv `cv` from its output gradient dy and input x."""
+    n = dy.shape[0]
+    if cv.transposed:
+        p, q, r, c, sign = x, dy, cv.cin, cv.cout, -1
+    else:
+        p, q, r, c, sign = dy, x, cv.cout, cv.cin, 1
+    tiles = ops.wgrad_tiles(n, T, r, c, cv.k, cv.pad, ops.dt_code(dy.dtype), dil=cv.dil)
+    splits = max(1, min(512 // max(1, tiles), n // 512))
+    slabs = torch.empty(splits, r, cv.k * c, device=dy.device, dtype=F32)
+    ops.conv_wgrad(p, q, slabs, T=T, r_dim=r, c_dim=c, ntaps=cv.k, pad=cv.pad, dil=cv.dil, shift_sign=sign,
+                   splits=splits)
+    return _unpack_grad(slabs, cv.transposed, cv.k)
+
+
+def _fwd(cv, x, w, y, T, **kw):
+    return ops.conv_fwd(x, w, y, T=T, cin=cv.cin, cout=cv.cout, ntaps=cv.k, pad=cv.pad, dil=cv.dil, **kw)
+
+
+def _dgrad(cv, dy, w, dx, T, **kw):
+    return ops.conv_dgrad(dy, w, dx, T=T, cin=cv.cout, cout=cv.cin, ntaps=cv.k, pad=(cv.k - 1) * cv.dil - cv.pad,
+                          dil=cv.dil, **kw)
+
+
+def _colsum(x, part):
+    out = torch.empty(x.shape[1], device=x.device, dtype=F32)
+    return ops.colsum(x, part, out)
+
+
+class _Plan:
+    """Static description of a Decoder for _DecoderFn (no tensors)."""
+
+    def __init__(self, dec):
+        self.dt = _DT[dec.compute_dtype]
+        self.steps, at = [], 0  # ("conv", _Conv) | ("block", conv_in, conv_cond, res_skip, at of gamma)
+        for layer in dec.layers:
+            if isinstance(layer, ResSkipBlock):
+                ci, cc, rs = _Conv(layer.conv_in, at), _Conv(layer.conv_cond, at + 2), _Conv(layer.res_skip_layers, at + 6)
+                self.steps.append(("block", ci, cc, rs, at + 4))
+                at += 8
+            elif isinstance(layer, WNConv1d):
+                self.steps.append(("conv", _Conv(layer, at)))
+                at += 2
+            else:
+                raise NotImplementedError("resampling decoder stages are not built for the hierarchical decoder")
+        if self.steps[-1][0] != "block" or any(a[0] == b[0] == "conv" for a, b in zip(self.steps, self.steps[1:])):
+            raise NotImplementedError("every decoder stage needs at least one ResSkip block")
+        self.fin1, self.fin2 = _Conv(dec.final_layer[1], at), _Conv(dec.final_layer[3], at + 2)
+        self.n_tensors = at + 4
+        self.scale = math.sqrt(1.0 / len(dec.layers))
+        self.S, self.final, self.cond = dec.skip_ch, dec.final_ch, dec.cond_ch
+
+    @staticmethod
+    def tensors(dec):
+        """The flat tensor list the plan indexes: per conv (w, bias), per block
+        conv_in, conv_cond, GroupNorm (gamma, beta), res_skip; then the final convs."""
+        out = []
+        for layer in dec.layers:
+            if isinstance(layer, ResSkipBlock):
+                out += [layer.conv_in.effective_weight(), layer.conv_in.bias, layer.conv_cond.effective_weight(),
+                        layer.conv_cond.bias, layer.norm_layer.weight, layer.norm_layer.bias,
+                        layer.res_skip_layers.effective_weight(), layer.res_skip_layers.bias]
+            else:
+                out += [layer.effective_weight(), layer.bias]
+        for i in (1, 3):
+            out += [dec.final_layer[i].effective_weight(), dec.final_layer[i].bias]
+        return out
+
+
+class _DecoderFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, save, T_levels, x, *rest):
+        nl = max(1, len(T_levels))
+        cin, ts = rest[:nl], rest[nl:]
+        if not x.is_cuda or not all(t.is_cuda for t in rest):
+            raise L.VqxError("vqvae2.Decoder runs on the MI355X only (libvqx); move it and its inputs with .cuda()")
+        dev, dt = x.device, plan.dt
+        B, _, T = x.shape
+        N = B * T
+        ts = [t.detach().float() for t in ts]
+        e = functools.partial(torch.empty, device=dev)
+        # conditioning at its own rate: c_low [B*Tc, cond] f32
+        rows = [_to_rows(z) for z in cin]
+        if T_levels:
+            Tc = choose_tc(T, T_levels)
+            c_low = ops.upsample_cat_fwd(rows, B, Tc, e(B * Tc, plan.cond, dtype=F32))
+        else:
+            Tc, c_low = T, rows[0]
+        x2 = e(N, x.shape[1], dtype=dt)
+        ops.nct_to_ntc(x.float().contiguous(), x2)
+        skip32 = e(N, plan.S, dtype=F32)
+        gn_part = e(B * 2 * 24, dtype=F32)
+        wp, saved, first = {}, [], True  # packed weights by tensor index; per step what the backward reads
+        cur = x2
+        for st in plan.steps:
+            if st[0] == "conv":
+                cv = st[1]
+                w = wp[cv.at] = _pack(ts[cv.at], cv.transposed, dt)
+                y = e(N, cv.cout, dtype=dt)
+                _fwd(cv, cur, w, y, T, bias=ts[cv.at + 1])
+                saved.append((cur,))
+                cur = y
+                continue
+            _, ci, cc, rs, ag = st
+            C = ci.cin
+            w_in, w_rs = _pack(ts[ci.at], True, dt), _pack(ts[rs.at], False, dt)
+            w_cc = _pack(ts[cc.at], False, F32)
+            wp[ci.at], wp[cc.at], wp[rs.at] = w_in, w_cc, w_rs
+            P = e(B * Tc, 2 * C, dtype=F32)  # conv_cond(c) + its bias, one row per conditioning frame
+            _fwd(cc, c_low, w_cc, P, Tc, bias=ts[cc.at + 1])
+            u, g, mr = e(N, 2 * C, dtype=dt), e(N, C, dtype=dt), e(B, 2, 2, dtype=F32)
+            seg = dict(rowbias=P, rowbias_T=Tc if Tc > 1 else 0)
+            if T % 128 == 0 and C % 128 == 0:  # GroupNorm statistics from the GEMM's epilogue tiles
+                gst = e((N // 128) * (2 * C // 128) * 4, dtype=F32)
+                _fwd(ci, cur, w_in, u, T, bias=ts[ci.at + 1], gn_stats=gst, gn_groups=2, **seg)
+                ops.gn_glu_fwd_tiles(u, g, T, gst, mr, ts[ag], ts[ag + 1])
+            else:
+                _fwd(ci, cur, w_in, u, T, bias=ts[ci.at + 1], **seg)
+                ops.groupnorm_stats(u, T, 2, gn_part, mr)
+                ops.gn_glu_fwd(u, g, T, mr, ts[ag], ts[ag + 1])
+            y = e(N, C, dtype=dt)
+            _fwd(rs, g, w_rs, y, T, bias=ts[rs.at + 1], res=cur, out2=skip32, split_col=C, out2_accumulate=not first)
+            first = False
+            saved.append((cur, u, g, mr))
+            cur = y
+        a_skip, f1 = e(N, plan.S, dtype=dt), e(N, plan.fin1.cout, dtype=dt)
+        xhat = e(N, plan.final, dtype=F32)
+        ops.scale_act_2d(skip32, a_skip, plan.scale, L.PRO_RELU)
+        w1, w2 = _pack(ts[plan.fin1.at], False, dt), _pack(ts[plan.fin2.at], False, dt)
+        _fwd(plan.fin1, a_skip, w1, f1, T, bias=ts[plan.fin1.at + 1], act=L.PRO_RELU)
+        _fwd(plan.fin2, f1, w2, xhat, T, bias=ts[plan.fin2.at + 1], out_f32=True)
+        if save:
+            wp[plan.fin1.at], wp[plan.fin2.at] = w1, w2
+            ctx.plan, ctx.dims, ctx.T_levels, ctx.Tc = plan, (B, T), T_levels, Tc
+            ctx.level_shapes = [tuple(z.shape) for z in cin]
+            ctx.keep = (saved, wp, a_skip, f1, c_low, ts)
+        return _to_nct(xhat, B, T)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        plan, (B, T), Tc = ctx.plan, ctx.dims, ctx.Tc
+        saved, wp, a_skip, f1, c_low, ts = ctx.keep
+        dev, dt, S = dout.device, plan.dt, plan.S
+        N = B * T
+        e = functools.partial(torch.empty, device=dev)
+        grads = [None] * plan.n_tensors
+        Cmax = max(st[1].cin for st in plan.steps if st[0] == "block")
+        cs_part = e(64 * max(2 * Cmax, Cmax + S, plan.final, plan.cond, 1024), dtype=F32)
+        gnb_part = e(B * 64 * 2, dtype=F32)
+        # final layer: ReLU, conv, ReLU, conv on scale * sum(skips)
+        dxhat = e(N, plan.final, dtype=dt)
+        ops.nct_to_ntc(dout.float().contiguous(), dxhat)
+        f1c, f2c = plan.fin1, plan.fin2
+        grads[f2c.at + 1] = _colsum(dxhat, cs_part)
+        grads[f2c.at] = _wgrad(f2c, dxhat, f1, T)
+        df1 = e(N, f2c.cin, dtype=dt)
+        _dgrad(f2c, dxhat, wp[f2c.at], df1, T, mask=f1, mask_slope=0.0)
+        grads[f1c.at + 1] = _colsum(df1, cs_part)
+        grads[f1c.at] = _wgrad(f1c, df1, a_skip, T)
+        # dr: [dL/dx | dL/dskip] of the current block's output, two buffers per width in turn
+        bufs = {}
+
+        def dr(C, k):
+            if (C, k) not in bufs:
+                bufs[(C, k)] = e(N, C + S, dtype=dt)
+                if (C, k) != first_key:
+                    ops.convert_2d(bufs[first_key][:, first_key[0]:], bufs[(C, k)][:, C:])
+            return bufs[(C, k)]
+
+        C_last = plan.steps[-1][1].cin
+        first_key = (C_last, 0)
+        cur = dr(C_last, 0)
+        _dgrad(f1c, df1, wp[f1c.at], cur[:, C_last:], T, mask=a_skip, mask_slope=0.0, mask_scale=plan.scale)
+        ops.convert_2d(None, cur, cols=C_last)  # dL/dx at the decoder output is 0: the last residual is unused
+        k, dc, dx = 0, None, None
+        for st, sv in zip(reversed(plan.steps), reversed(saved)):
+            if st[0] == "conv":
+                cv = st[1]
+                cur_x = cur[:, :cv.cout]
+                grads[cv.at + 1] = _colsum(cur_x, cs_part)
+                grads[cv.at] = _wgrad(cv, cur_x, sv[0], T)
+                if sv[0] is saved[0][0]:  # the decoder input
+                    dx = e(N, cv.cin, dtype=F32)
+                    _dgrad(cv, cur_x, wp[cv.at], dx, T, out_f32=True)
+                else:
+                    k ^= 1
+                    nxt = dr(cv.cin, k)
+                    _dgrad(cv, cur_x, wp[cv.at], nxt[:, :cv.cin], T)
+                    cur = nxt
+                continue
+            _, ci, cc, rs, ag = st
+            xin, u, g, mr = sv
+            C = ci.cin
+            grads[rs.at + 1] = _colsum(cur, cs_part)
+            grads[rs.at] = _wgrad(rs, cur, g, T)
+            dg, du = e(N, C, dtype=dt), e(N, 2 * C, dtype=dt)
+            _dgrad(rs, cur, wp[rs.at], dg, T)
+            cs_b, dgam_b, dbet_b = (e(B, 2 * C, dtype=F32) for _ in range(3))
+            ops.gn_bwd(dg, u, du, T, 2, True, mr, ts[ag], ts[ag + 1], gnb_part, cs_b, dgam_b, dbet_b)
+            grads[ci.at + 1] = _colsum(cs_b, cs_part)
+            grads[ag], grads[ag + 1] = _colsum(dgam_b, cs_part), _colsum(dbet_b, cs_part)
+            # conditioning: dP = the per-segment sums of du, then conv_cond's own gradients at the low rate
+            if Tc == 1:
+                dP = cs_b
+            else:
+                dP = e(B * Tc, 2 * C, dtype=F32)
+                ops.upsample_cat_bwd([dP], B, T, du)
+            grads[cc.at + 1] = grads[ci.at + 1] if Tc == 1 else _colsum(dP, cs_part)
+            grads[cc.at] = _wgrad(cc, dP, c_low, Tc)
+            dc_new = e(B * Tc, plan.cond, dtype=F32)
+            _dgrad(cc, dP, wp[cc.at], dc_new, Tc, **({} if dc is None else dict(res=dc)))
+            dc = dc_new
+            grads[ci.at] = _wgrad(ci, du, xin, T)
+            k ^= 1
+            nxt = dr(C, k)
+            _dgrad(ci, du, wp[ci.at], nxt[:, :C], T, res=cur[:, :C])
+            cur = nxt
+        # the conditioning's gradient back to the levels (or to the tensor c)
+        if ctx.T_levels:
+            dl = [e(B * Tl, Cl, dtype=F32) for _, Cl, Tl in ctx.level_shapes]
+            ops.upsample_cat_bwd(dl, B, Tc, dc)
+            dcin = [_to_nct(d, B, s[2]) for d, s in zip(dl, ctx.level_shapes)]
+        else:
+            dcin = [_to_nct(dc, B, T)]
+        ctx.keep = None
+        return (None, None, None, _to_nct(dx, B, T), *dcin, *grads)
+
+
+class Decoder(_Decoder):
+    """vqvae2.py:274-371 with `compute_dtype: fp32|bf16`; forward((x, c)) with c a
+    (B, cond, T) tensor or a list of levels (B, C_l, T_l), sum C_l == cond."""
+
+    def __init__(self, *args, compute_dtype="fp32", **kw):
+        scales = kw.get("upsample_scales", args[2] if len(args) > 2 else (1, 1, 1, 1))
+        if any(s != 1 for s in scales):
+            raise NotImplementedError(f"vqvae2.Decoder: upsample_scales {list(scales)}: resampling stages are not "
+                                      "built for the hierarchical decoder (the vae2 recipe has none)")
+        if compute_dtype not in _DT:
+            raise ValueError(f"compute_dtype {compute_dtype!r} is not fp32 or bf16")
+        super().__init__(*args, **kw)
+        self.compute_dtype = compute_dtype
+        self._plan = None
+
+    def forward(self, input):
+        x, c = input
+        if x.dim() != 3:
+            raise ValueError(f"vqvae2.Decoder: x {tuple(x.shape)} is not (B, C, T)")
+        B, _, T = x.shape
+        levels = [c] if torch.is_tensor(c) else list(c)
+        if not levels or any(z.dim() != 3 or z.shape[0] != B for z in levels) \
+                or sum(z.shape[1] for z in levels) != self.cond_ch:
+            raise ValueError(f"vqvae2.Decoder: the conditioning must be (B, C_l, T_l) levels with sum C_l == "
+                             f"{self.cond_ch}")
+        if torch.is_tensor(c):
+            if c.shape[2] != T:
+                raise ValueError(f"vqvae2.Decoder: a tensor c must have x's {T} frames, got {c.shape[2]}")
+            T_levels = ()
+        else:
+            T_levels = tuple(z.shape[2] for z in levels)
+            for Tl in T_levels:
+                src_index(T, Tl)
+        if self._plan is None:
+            self._plan = _Plan(self)
+        ts = _Plan.tensors(self)
+        save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, *levels, *ts))
+        return _DecoderFn.apply(self._plan, save, T_levels, x, *levels, *ts)

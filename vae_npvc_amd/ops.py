@@ -67,7 +67,7 @@ def _conv_extents(x, w, y, a, bias, rowbias, res, mask, out2, y2, colsum, stats,
     _span(w, cout * a.ntaps * cin, "conv w")
     _rows(y, n, a.ldy, split or cout, "conv y")
     _span(bias, cout, "conv bias")
-    _span(rowbias, (n // max(1, a.T)) * cout, "conv rowbias")
+    _span(rowbias, (n // max(1, a.T)) * max(1, a.rowbias_T) * cout, "conv rowbias")
     _rows(res, n, a.ldres, split or cout, "conv res")
     _rows(mask, n, a.ldmask, cout, "conv mask")
     _rows(out2, n, a.ldo2, cout - split, "conv out2")
@@ -113,7 +113,7 @@ def conv_args(x, w, y, *, T, cin, cout, ntaps, pad, prologue=L.PRO_NONE, pro_sca
               rowbias=None, res=None, mask=None, mask_slope=0.0, mask_scale=1.0, gn_h=None, gn_mr=None,
               gn_gamma=None, gn_beta=None, out2=None, split_col=0, out2_accumulate=False, out_f32=False,
               act=None, y2=None, colsum=None, gn_stats=None, gn_bwd=None, gn_groups=1, gn_glu=False,
-              gn_tiles=None, gn_eps=1e-5, dil=1, policy=None):
+              gn_tiles=None, gn_eps=1e-5, dil=1, policy=None, rowbias_T=0):
     epi = 0
     if bias is not None:
         epi |= L.EPI_BIAS
@@ -145,6 +145,7 @@ def conv_args(x, w, y, *, T, cin, cout, ntaps, pad, prologue=L.PRO_NONE, pro_sca
     a.gn_h, a.gn_mean_rstd, a.gn_gamma, a.gn_beta, a.out2 = ptr(gn_h), ptr(gn_mr), ptr(gn_gamma), ptr(gn_beta), ptr(out2)
     a.n_rows, a.T, a.cin, a.cout, a.ntaps, a.pad, a.dil = x.shape[0], T, cin, cout, ntaps, pad, dil
     a.kernel_policy = _policy if policy is None else policy
+    a.rowbias_T = rowbias_T  # > 1: rowbias [B*rowbias_T, cout], one row per stretch segment (forward only)
     a.ldx, a.ldy = x.stride(0), y.stride(0)
     a.ldres = res.stride(0) if res is not None else 0
     a.ldmask = mask.stride(0) if mask is not None else 0
@@ -977,6 +978,49 @@ def gst_bwd(z, T, params, heads, d_style, ws, dz, grads):
     _rows(dz, dz.shape[0], a.lddz, a.R, "gst_bwd dz")
     call("vqx_gst_bwd", ctypes.byref(a), stream_ptr())
     return dz
+
+
+HIER_MAX_LEVELS = 8  # include/vqx.h vqx_upsample_cat_*
+
+
+def _hier_levels(levels, B, what):
+    """vqx_hier_level array of frame-major f32 levels [B*T_l, C_l] (rows of stride(0))."""
+    if not 1 <= len(levels) <= HIER_MAX_LEVELS:
+        raise ValueError(f"{what}: {len(levels)} levels, 1..{HIER_MAX_LEVELS} are supported")
+    _check_cuda(*levels)
+    arr = (L.HierLevel * len(levels))()
+    for e, z in zip(arr, levels):
+        if z.dtype != torch.float32 or z.dim() != 2 or z.stride(1) != 1 or z.shape[0] % B:
+            raise ValueError(f"{what}: a level must be f32 [B*T_l, C_l] rows with unit column stride")
+        e.z, e.T_l, e.C, e.ld = ptr(z), z.shape[0] // B, z.shape[1], z.stride(0)
+        _rows(z, z.shape[0], e.ld, e.C, f"{what} level")
+    return arr
+
+
+def upsample_cat_fwd(levels, B, T, out):
+    """out[b*T + t, off_l + c] = levels[l][b*T_l + min(t // (T // T_l), T_l - 1), c]
+    (vqx_upsample_cat_fwd): the levels stretched to T frames by repetition and
+    stacked on channels; out f32 or bf16 [B*T, >= sum C_l]."""
+    arr = _hier_levels(levels, B, "upsample_cat_fwd")
+    _check_cuda(out)
+    if out.dim() != 2 or out.shape[0] != B * T or out.stride(1) != 1:
+        raise ValueError(f"upsample_cat_fwd: out must be [{B * T}, C] rows with unit column stride")
+    _rows(out, out.shape[0], out.stride(0), sum(z.shape[1] for z in levels), "upsample_cat_fwd out")
+    call("vqx_upsample_cat_fwd", arr, len(levels), B, T, ptr(out), out.stride(0), dt_code(out.dtype), stream_ptr())
+    return out
+
+
+def upsample_cat_bwd(dlevels, B, T, dout):
+    """The adjoint: dlevels[l][b*T_l + s, c] = the sum of dout[b*T + t, off_l + c]
+    over the frames t stretched from s, in fp32 in a fixed order (overwritten;
+    vqx_upsample_cat_bwd).  With one level of dout's width: per-segment column sums."""
+    arr = _hier_levels(dlevels, B, "upsample_cat_bwd")
+    _check_cuda(dout)
+    if dout.dim() != 2 or dout.shape[0] != B * T or dout.stride(1) != 1:
+        raise ValueError(f"upsample_cat_bwd: dout must be [{B * T}, C] rows with unit column stride")
+    _rows(dout, dout.shape[0], dout.stride(0), sum(z.shape[1] for z in dlevels), "upsample_cat_bwd dout")
+    call("vqx_upsample_cat_bwd", arr, len(dlevels), B, T, ptr(dout), dout.stride(0), dt_code(dout.dtype), stream_ptr())
+    return dlevels
 
 
 def cu_masked_stream(reserve_cus):
