@@ -40,6 +40,20 @@ def test_library_exports_every_header_symbol():
     assert set(header_functions()) <= set(L._SIGS) | {"vqx_last_error", "vqx_version"}
 
 
+def test_build_lists_name_every_source_and_header():
+    """csrc/build.py compiles what SOURCES names and rebuilds on what HEADERS
+    names: a .hip outside SOURCES is never linked, a .h outside HEADERS leaves
+    stale objects after an edit."""
+    from vae_npvc_amd.csrc import build
+    on_disk = {p.name for p in build.HERE.glob("*.hip")}
+    assert set(build.SOURCES) == on_disk, sorted(set(build.SOURCES) ^ on_disk)
+    assert len(build.SOURCES) == len(set(build.SOURCES))
+    missing = [s for s in build.SOURCES if not (build.HERE / s).is_file()]
+    assert not missing, missing
+    unlisted = {p.name for p in build.HERE.glob("*.h")} - set(build.HEADERS)
+    assert not unlisted, sorted(unlisted)
+
+
 def test_abi_version():
     L, lib = _lib()
     assert lib.vqx_version() == L.ABI_VERSION

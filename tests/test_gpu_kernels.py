@@ -528,7 +528,7 @@ def test_linear_batched_and_colreduce():
 @pytest.mark.parametrize("B", [64, 13, 200])
 def test_linear_cond_fast_path_equals_tiled_kernels(B):
     """The fp32-MFMA conditioning kernels (I = 128, B <= 64, 16-B aligned c;
-    vqx_misc.hip linear_cond_*) and the 64x64-tiled kernels the same call
+    vqx_linear.hip linear_cond_*) and the 64x64-tiled kernels the same call
     takes for an unaligned c, both against float64 (the config-2 shape: 10
     layers, O = 1024; B = 13 leaves rows of the tiles empty).  Their summation
     orders differ (round 5), so the bar is fp32 rounding: 1e-6 relative."""
@@ -1376,7 +1376,7 @@ def test_wgrad_in_launch_split_k_reduction(r, c, shift, splits, B, T):
     kw = dict(T=T, r_dim=r, c_dim=c, ntaps=3, pad=1, shift_sign=shift, splits=splits)
     ref_slabs = torch.empty(splits, r, 3 * c, device=DEV, dtype=torch.bfloat16)
     ops.conv_wgrad(p, q, ref_slabs, **kw)
-    # the weight-norm backward's order (vqx_misc.hip wn_bwd_kernel, 256-thread blocks): one
+    # the weight-norm backward's order (vqx_wn.hip wn_bwd_kernel, 256-thread blocks): one
     # sequential sum for rows of >= 256 four-column groups, else G interleaved split groups
     nx4 = 3 * c // 4
     G = 1 if nx4 >= 256 else min(splits, 256 // nx4)

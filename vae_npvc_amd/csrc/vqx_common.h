@@ -1,4 +1,5 @@
-// Shared device helpers for libvqx (gfx950 / CDNA4 only).
+// Shared device helpers for libvqx (gfx950 / CDNA4 only), with the few host
+// helpers every unit uses.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,6 +17,17 @@ namespace vqx {
 
 void set_error(const char* fmt, ...);
 int launch_status(const char* what);
+
+// blocks of `block` threads covering n elements, at most `cap` (grid-stride kernels)
+inline int grid_for(int64_t n, int block = 256, int cap = 8192) {
+  int64_t g = (n + block - 1) / block;
+  if (g < 1) g = 1;
+  return (int)(g > cap ? cap : g);
+}
+
+// out[0] = scale * sum p[0..n) in one 1024-thread block (sum_partials_scale_kernel,
+// vqx_reduce.hip): the launcher for the other units (vqx_loss.hip, vqx_optim.hip)
+void sum_partials_scale_launch(const float* p, int n, float scale, float* out, hipStream_t s);
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((unsigned)v) << 16); }
 __device__ __forceinline__ bf16_t f2bf(float f) {
@@ -47,6 +59,25 @@ __device__ __forceinline__ float ld_dt(const void* p, int64_t i, int dt) {
 }
 __device__ __forceinline__ void st_dt(void* p, int64_t i, float v, int dt) {
   if (dt == VQX_BF16) ((bf16_t*)p)[i] = f2bf(v); else ((float*)p)[i] = v;
+}
+
+// NCT (f32) -> NTC: one 32 x 32 tile (bx over T, by over C, b the batch row);
+// tile: LDS.  The body of nct_to_ntc_kernel (vqx_layout.hip) and of the step
+// prologue's transpose blocks (vqx_linear.hip).
+template <typename T>
+__device__ __forceinline__ void nct_to_ntc_tile(const float* __restrict__ x, int C, int T_, T* __restrict__ y, int ldy,
+                                                int bx, int by, int b, float (*tile)[33]) {
+  const int t0 = bx * 32, c0 = by * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 256 threads: 8 rows per pass
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    tile[i][tx] = (c < C && t < T_) ? x[((int64_t)b * C + c) * T_ + t] : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    if (c < C && t < T_) Elem<T>::st(y, ((int64_t)b * T_ + t) * ldy + c, tile[tx][i]);
+  }
 }
 
 // GLU activations with the hardware reciprocal (v_rcp_f32, 1 ulp) instead of

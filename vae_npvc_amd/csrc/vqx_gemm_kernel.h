@@ -1587,7 +1587,7 @@ __device__ __forceinline__ void wgrad_tile_fixup(const GemmParams& P, int tmn, i
   // vqx_weight_norm_bwd's summation order for a row of Nc columns: one
   // sequential sum over the splits when the row has >= 256 four-column groups,
   // else G = min(S, 256 / groups) interleaved split groups added in group order
-  // (wn_bwd_kernel, 256-thread blocks: vqx_misc.hip kWnThreads)
+  // (wn_bwd_kernel, 256-thread blocks: vqx_wn.hip kWnThreads)
   const int nx4 = P.Nc / 4;
   const int G = nx4 >= 256 ? 1 : (S < 256 / nx4 ? S : 256 / nx4);
   // chunk (j, pass): row r0 + pass*32 + tid/8, columns j*cdim + c0 + (tid%8)*8 .. +7

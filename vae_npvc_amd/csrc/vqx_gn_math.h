@@ -1,4 +1,4 @@
-// GroupNorm(/GLU)-backward element math of the apply kernel (vqx_misc.hip
+// GroupNorm(/GLU)-backward element math of the apply kernel (vqx_gn.hip
 // gn_bwd_apply_vec_kernel), kept in one header so any other kernel applying it
 // (the measured-and-rejected fused 1x1 DGRAD apply, tools/lab/
 // dual_k1g_apply.patch) produces the same dx bit for bit.  Reference: autograd

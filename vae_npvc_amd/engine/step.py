@@ -130,7 +130,7 @@ def _tm(N):
 
 def _wn_block_bytes(e):
     """Approximate HBM bytes one workgroup of vqx_weight_norm_bwd moves for a
-    table entry (csrc/vqx_misc.hip wn_bwd_kernel): a column-reduce block
+    table entry (csrc/vqx_wn.hip wn_bwd_kernel): a column-reduce block
     reads 32 columns of every partial row; a row block reads the row's
     split-K slabs and v and writes dv (four rows per block on the 1x1
     wave-per-row path)."""
