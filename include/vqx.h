@@ -655,6 +655,18 @@ int vqx_vq_plain_bwd(const float* z, const float* z_norm, const float* z_len, co
                      const float* bcnt, const float* emb, const float* e_len, int32_t K, float* dE,
                      vqx_stream_t stream);
 
+/* vqx_vq_plain_bwd for a quantizer level inside autograd (no readback, no
+ * jitter map): the weights of the two loss terms given apart, z_qut by s_qut
+ * (vqx_vq_plain_bwd's scale) and z_enc by s_enc (its beta * scale), each
+ * multiplied by an upstream gradient read from the device, g_qut[0] and
+ * g_enc[0]; a NULL pointer stands for 1, and with both NULL the result has
+ * vqx_vq_plain_bwd's bits.  Additive: the ABI version does not change. */
+int vqx_vq_plain_bwd_g(const float* z, const float* z_norm, const float* z_len, const float* zq, const void* dzq,
+                       int32_t T, int64_t n_rows, int32_t D, int32_t normalize, float s_qut, float s_enc,
+                       const float* g_qut, const float* g_enc, void* dz, int32_t dtype, const float* bsum,
+                       const float* bcnt, const float* emb, const float* e_len, int32_t K, float* dE,
+                       vqx_stream_t stream);
+
 /* dst[r][c] = act(scale * src[r][c]) with dtype conversion (act = VQX_PRO_*;
  * the decoder's ReLU(sqrt(1/11) * skip) operand, vqvae.py:316-317). */
 int vqx_scale_act_2d(const void* src, int32_t ld_src, int32_t src_dtype, void* dst, int32_t ld_dst,
@@ -792,6 +804,29 @@ int vqx_upsample_cat_fwd(const vqx_hier_level* levels, int32_t n_levels, int32_t
                          int32_t ldo, int32_t out_dtype, vqx_stream_t stream);
 int vqx_upsample_cat_bwd(const vqx_hier_level* levels, int32_t n_levels, int32_t B, int32_t T, const void* dout,
                          int32_t ldo, int32_t dout_dtype, vqx_stream_t stream);
+
+/*
+ * Masked layout change of the hierarchical encoder's backward (vqvae2.py:
+ * 238-246, the encoder's second output `feat` = LeakyReLU_0.2(a)): the f32
+ * (B, C, T) gradient into `feat`, through that LeakyReLU, frame-major:
+ *   dst[b*T + t][c] = g_nct[b][c][t] * (a[b*T + t][c] > 0 ? 1 : slope)
+ * One f32 product, rounded once to dst_dtype (VQX_F32 | VQX_BF16); `a` is the
+ * stored activation [B*T][lda] in a_dtype (only its sign is read).  The result
+ * is the `res` operand of the z_proj DGRAD whose epilogue applies MASK before
+ * RES, so the sum is lrelu'(a) * (W^T dz + dfeat).  Any B, C, T >= 1
+ * (B <= 65535); lda, lddst >= C; no alignment requirement.  Additive: the ABI
+ * version does not change.
+ */
+int vqx_nct_to_ntc_lrelu_bwd(const float* g_nct, int32_t B, int32_t C, int32_t T, const void* a, int32_t lda,
+                             int32_t a_dtype, float slope, void* dst, int32_t lddst, int32_t dst_dtype,
+                             vqx_stream_t stream);
+
+/* x_nct[b][c][t] = y[b*T + t][c] * g[0]: vqx_ntc_to_nct of an f32 frame-major
+ * matrix with one device scalar folded in (the gradient of log_loss into xhat
+ * times its upstream gradient, without a readback or a second pass).  Any
+ * B, C, T >= 1 (B <= 65535), ldy >= C.  Additive: the ABI version stays. */
+int vqx_ntc_to_nct_scale(const float* y, int32_t ldy, int32_t B, int32_t C, int32_t T, const float* g,
+                         float* x_nct, vqx_stream_t stream);
 
 /* ABI 130: vqx_conv_args.rowbias_T appended (segmented row bias of the forward
  * epilogue; 0 or 1 keeps every earlier call's bits) and vqx_upsample_cat_*. */

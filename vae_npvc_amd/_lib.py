@@ -173,6 +173,9 @@ _SIGS = {
     "vqx_vq_plain_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32,
                          c_int32, c_float, c_float, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_int32, c_void_p, c_void_p],
+    "vqx_vq_plain_bwd_g": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32,
+                           c_float, c_float, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_int32, c_void_p, c_void_p],
     "vqx_stream_create_cu_mask": [c_int32, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int32)],
     "vqx_mailbox_create": [c_int32, c_int32, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p)],
     "vqx_mailbox_destroy": [c_void_p],
@@ -199,6 +202,9 @@ _SIGS = {
                              c_void_p],
     "vqx_upsample_cat_bwd": [ctypes.POINTER(HierLevel), c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
                              c_void_p],
+    "vqx_ntc_to_nct_scale": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p],
+    "vqx_nct_to_ntc_lrelu_bwd": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float, c_void_p,
+                                 c_int32, c_int32, c_void_p],
 }
 EXPORTS = tuple(_SIGS) + ("vqx_last_error", "vqx_version")
 

@@ -19,6 +19,16 @@
 // segment of the call (the tail segment T - (T_l - 1) * (T / T_l) of some
 // level) is below 32 frames, else 8; it depends on the shapes alone, so two
 // calls with the same shapes give the same bits.
+//
+// Masked layout change of the hierarchical encoder's backward (include/vqx.h
+// vqx_nct_to_ntc_lrelu_bwd): the (B, C, T) f32 gradient autograd hands to the
+// encoder's second output, through the LeakyReLU that produced it, as the
+// frame-major operand of the next GEMM's residual epilogue:
+//   hier_lrelu_bwd_kernel  one 32 x 32 (frames x channels) tile a workgroup,
+//             transposed through LDS as nct_to_ntc_tile does (reads run along
+//             T, writes along C): dst[b*T + t][c] = g[b][c][t] * (a[b*T + t][c]
+//             > 0 ? 1 : slope), one f32 product rounded once to the
+//             destination type.
 #include "vqx_common.h"
 
 namespace vqx {
@@ -148,6 +158,49 @@ __global__ __launch_bounds__(HIER_BWD_LANES* HIER_BWD_PARTS) void hier_cat_bwd_k
   }
 }
 
+template <typename TA, typename TD>
+__global__ __launch_bounds__(256) void hier_lrelu_bwd_kernel(const float* __restrict__ g, int C, int T,
+                                                             const TA* __restrict__ a, int64_t lda, float slope,
+                                                             TD* __restrict__ dst, int64_t ldd) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z;
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 256 threads: 8 rows per pass
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    tile[i][tx] = (c < C && t < T) ? g[((int64_t)b * C + c) * T + t] : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    if (c < C && t < T) {
+      const int64_t row = (int64_t)b * T + t;
+      const float m = Elem<TA>::ld(a, row * lda + c) > 0.f ? 1.f : slope;
+      Elem<TD>::st(dst, row * ldd + c, tile[tx][i] * m);
+    }
+  }
+}
+
+// x[b][c][t] = y[b*T + t][c] * g[0]: vqx_ntc_to_nct (vqx_layout.hip) with one device scalar folded in.
+__global__ __launch_bounds__(256) void hier_ntc_to_nct_scale_kernel(const float* __restrict__ y, int64_t ldy, int C,
+                                                                    int T, const float* __restrict__ g,
+                                                                    float* __restrict__ x) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z;
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const float s = *g;
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    tile[i][tx] = (c < C && t < T) ? y[((int64_t)b * T + t) * ldy + c] : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    if (c < C && t < T) x[((int64_t)b * C + c) * T + t] = tile[tx][i] * s;
+  }
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // Checks shared by both directions; fills the by-value table.  `v8` = every
@@ -228,4 +281,46 @@ extern "C" int vqx_upsample_cat_bwd(const vqx_hier_level* levels, int32_t n_leve
   auto* fn = dout_dtype == VQX_BF16 ? hier_cat_bwd_kernel<true> : hier_cat_bwd_kernel<false>;
   hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(HIER_BWD_LANES, P), 0, s, L, items, T, dout, (int64_t)ldo);
   return launch_status("vqx_upsample_cat_bwd");
+}
+
+extern "C" int vqx_nct_to_ntc_lrelu_bwd(const float* g_nct, int32_t B, int32_t C, int32_t T, const void* a, int32_t lda,
+                                        int32_t a_dtype, float slope, void* dst, int32_t lddst, int32_t dst_dtype,
+                                        vqx_stream_t stream) {
+  const char* who = "vqx_nct_to_ntc_lrelu_bwd";
+  if (!g_nct || !a || !dst) { set_error("%s: null pointer", who); return -1; }
+  if ((a_dtype != VQX_F32 && a_dtype != VQX_BF16) || (dst_dtype != VQX_F32 && dst_dtype != VQX_BF16)) {
+    set_error("%s: bad dtype %d / %d", who, a_dtype, dst_dtype);
+    return -1;
+  }
+  if (B < 1 || C < 1 || T < 1 || B > 65535 || (C + 31) / 32 > 65535) {
+    set_error("%s: B = %d, C = %d, T = %d (1 <= B <= 65535, 1 <= C <= 2097120, T >= 1)", who, B, C, T);
+    return -1;
+  }
+  if (lda < C || lddst < C) { set_error("%s: lda = %d / lddst = %d below C = %d", who, lda, lddst, C); return -1; }
+  const dim3 grid((unsigned)((T + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)B);
+  hipStream_t s = (hipStream_t)stream;
+#define VQX_HIER_LRELU(TA, TD)                                                                                  \
+  hipLaunchKernelGGL((hier_lrelu_bwd_kernel<TA, TD>), grid, dim3(256), 0, s, g_nct, C, T, (const TA*)a, (int64_t)lda, \
+                     slope, (TD*)dst, (int64_t)lddst)
+  if (a_dtype == VQX_BF16) {
+    if (dst_dtype == VQX_BF16) VQX_HIER_LRELU(bf16_t, bf16_t); else VQX_HIER_LRELU(bf16_t, float);
+  } else {
+    if (dst_dtype == VQX_BF16) VQX_HIER_LRELU(float, bf16_t); else VQX_HIER_LRELU(float, float);
+  }
+#undef VQX_HIER_LRELU
+  return launch_status(who);
+}
+
+extern "C" int vqx_ntc_to_nct_scale(const float* y, int32_t ldy, int32_t B, int32_t C, int32_t T, const float* g,
+                                    float* x_nct, vqx_stream_t stream) {
+  const char* who = "vqx_ntc_to_nct_scale";
+  if (!y || !g || !x_nct) { set_error("%s: null pointer", who); return -1; }
+  if (B < 1 || C < 1 || T < 1 || B > 65535 || (C + 31) / 32 > 65535 || ldy < C) {
+    set_error("%s: B = %d, C = %d, T = %d, ldy = %d (1 <= B <= 65535, C, T >= 1, ldy >= C)", who, B, C, T, ldy);
+    return -1;
+  }
+  const dim3 grid((unsigned)((T + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)B);
+  hipLaunchKernelGGL(hier_ntc_to_nct_scale_kernel, grid, dim3(256), 0, (hipStream_t)stream, y, (int64_t)ldy, C, T, g,
+                     x_nct);
+  return launch_status(who);
 }

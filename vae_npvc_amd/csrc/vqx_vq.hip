@@ -1034,12 +1034,18 @@ template <typename T, int PL>
 __global__ __launch_bounds__(256) void vq_plain_bwd_kernel(const float* __restrict__ z, const float* __restrict__ zn,
                                                            const float* __restrict__ zlen, const float* __restrict__ zq,
                                                            const T* __restrict__ dzq, const int* __restrict__ src_t,
-                                                           int Tn, int64_t N, int normalize, float beta, float s,
+                                                           int Tn, int64_t N, int normalize, float s, float bs,
                                                            T* __restrict__ dz, const float* __restrict__ bsum,
                                                            const float* __restrict__ bcnt,
                                                            const float* __restrict__ emb, const float* __restrict__ elen,
-                                                           int K, float* __restrict__ dE) {
+                                                           int K, float* __restrict__ dE,
+                                                           const float* __restrict__ g_qut,
+                                                           const float* __restrict__ g_enc) {
   constexpr int D = 64 * PL;
+  // s weighs z_qut, bs (= beta * s for vqx_vq_plain_bwd) z_enc; vqx_vq_plain_bwd_g
+  // multiplies each by its upstream gradient read from the device (NULL = 1)
+  if (g_qut) s *= *g_qut;
+  if (g_enc) bs *= *g_enc;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int kb = (K + 3) / 4;
   if ((int)blockIdx.x < kb) {
@@ -1070,7 +1076,6 @@ __global__ __launch_bounds__(256) void vq_plain_bwd_kernel(const float* __restri
   const bool st = dzq && (!src_t || src_t[t] == t);
 #pragma unroll
   for (int i = 0; i < PL; ++i) g.v[i] = st ? Elem<T>::ld(dzq, o + i) : 0.f;
-  const float bs = beta * s;
   RowPL<PL> d;
 #pragma unroll
   for (int i = 0; i < PL; ++i) d.v[i] = g.v[i] + bs * (u.v[i] - q.v[i]);
@@ -1114,31 +1119,53 @@ extern "C" int vqx_vq_perplexity(const float* counts, int32_t K, int64_t n_rows,
   return launch_status("vqx_vq_perplexity");
 }
 
-extern "C" int vqx_vq_plain_bwd(const float* z, const float* z_norm, const float* z_len, const float* zq,
-                                const void* dzq, const int32_t* src_t, int32_t T, int64_t n_rows, int32_t D,
-                                int32_t normalize, float beta, float scale, void* dz, int32_t dtype, const float* bsum,
-                                const float* bcnt, const float* emb, const float* e_len, int32_t K, float* dE,
-                                vqx_stream_t stream) {
-  if (!vq_d_ok(D)) { set_error("vqx_vq_plain_bwd: z_dim must be 64, 128 or 256 (got %d)", D); return -1; }
+namespace {
+int vq_plain_bwd_launch(const char* who, const float* z, const float* z_norm, const float* z_len, const float* zq,
+                        const void* dzq, const int32_t* src_t, int32_t T, int64_t n_rows, int32_t D, int32_t normalize,
+                        float s_qut, float s_enc, void* dz, int32_t dtype, const float* bsum, const float* bcnt,
+                        const float* emb, const float* e_len, int32_t K, float* dE, const float* g_qut,
+                        const float* g_enc, vqx_stream_t stream) {
+  if (!vq_d_ok(D)) { set_error("%s: z_dim must be 64, 128 or 256 (got %d)", who, D); return -1; }
   if (!z_norm || !zq || !dz || !bsum || !bcnt || !emb || !dE || T < 1 || n_rows < 1 || K < 1 ||
       (normalize && (!z || !z_len || !e_len))) {
-    set_error("vqx_vq_plain_bwd: bad arguments");
+    set_error("%s: bad arguments", who);
     return -1;
   }
   const int kb = (K + 3) / 4;
   const int64_t zb = (n_rows + 3) / 4;
+  if (kb + zb > INT32_MAX) { set_error("%s: %lld workgroups", who, (long long)(kb + zb)); return -1; }
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)(kb + zb));
   if (dtype == VQX_BF16) {
     auto* kfn = D == 64 ? vq_plain_bwd_kernel<bf16_t, 1> : D == 128 ? vq_plain_bwd_kernel<bf16_t, 2>
                                                                     : vq_plain_bwd_kernel<bf16_t, 4>;
     hipLaunchKernelGGL(kfn, grid, dim3(256), 0, s, z, z_norm, z_len, zq, (const bf16_t*)dzq, src_t, T, n_rows,
-                       normalize, beta, scale, (bf16_t*)dz, bsum, bcnt, emb, e_len, K, dE);
+                       normalize, s_qut, s_enc, (bf16_t*)dz, bsum, bcnt, emb, e_len, K, dE, g_qut, g_enc);
   } else {
     auto* kfn = D == 64 ? vq_plain_bwd_kernel<float, 1> : D == 128 ? vq_plain_bwd_kernel<float, 2>
                                                                    : vq_plain_bwd_kernel<float, 4>;
     hipLaunchKernelGGL(kfn, grid, dim3(256), 0, s, z, z_norm, z_len, zq, (const float*)dzq, src_t, T, n_rows,
-                       normalize, beta, scale, (float*)dz, bsum, bcnt, emb, e_len, K, dE);
+                       normalize, s_qut, s_enc, (float*)dz, bsum, bcnt, emb, e_len, K, dE, g_qut, g_enc);
   }
-  return launch_status("vqx_vq_plain_bwd");
+  return launch_status(who);
+}
+}  // namespace
+
+extern "C" int vqx_vq_plain_bwd(const float* z, const float* z_norm, const float* z_len, const float* zq,
+                                const void* dzq, const int32_t* src_t, int32_t T, int64_t n_rows, int32_t D,
+                                int32_t normalize, float beta, float scale, void* dz, int32_t dtype, const float* bsum,
+                                const float* bcnt, const float* emb, const float* e_len, int32_t K, float* dE,
+                                vqx_stream_t stream) {
+  const float s_enc = beta * scale;  // one f32 product, as the kernel formed it
+  return vq_plain_bwd_launch("vqx_vq_plain_bwd", z, z_norm, z_len, zq, dzq, src_t, T, n_rows, D, normalize, scale, s_enc,
+                             dz, dtype, bsum, bcnt, emb, e_len, K, dE, nullptr, nullptr, stream);
+}
+
+extern "C" int vqx_vq_plain_bwd_g(const float* z, const float* z_norm, const float* z_len, const float* zq,
+                                  const void* dzq, int32_t T, int64_t n_rows, int32_t D, int32_t normalize, float s_qut,
+                                  float s_enc, const float* g_qut, const float* g_enc, void* dz, int32_t dtype,
+                                  const float* bsum, const float* bcnt, const float* emb, const float* e_len, int32_t K,
+                                  float* dE, vqx_stream_t stream) {
+  return vq_plain_bwd_launch("vqx_vq_plain_bwd_g", z, z_norm, z_len, zq, dzq, nullptr, T, n_rows, D, normalize, s_qut,
+                             s_enc, dz, dtype, bsum, bcnt, emb, e_len, K, dE, g_qut, g_enc, stream);
 }

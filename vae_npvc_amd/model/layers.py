@@ -12,6 +12,9 @@ import math
 import torch
 import torch.nn as nn
 
+from .. import _lib as L
+from .. import ops
+
 
 class WNConv1d(nn.Module):
     """Weight-normed stride-1 Conv1d (kind 0, v [cout, cin, k], g [cout,1,1]) or
@@ -114,13 +117,43 @@ class ResSkipBlock(nn.Module):
         self.dilation = dilation
 
 
-class Conditions(nn.Module):
-    """Speaker embedding (layers.py:12-60, normalize=False => nn.Embedding)."""
+class _EmbeddingFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ids, weight):
+        if not (ids.is_cuda and weight.is_cuda):
+            raise L.VqxError("Conditions runs on the MI355X only (libvqx); move it and its ids with .cuda()")
+        flat = ids.reshape(-1).to(torch.int64).contiguous()
+        w = weight.detach().float().contiguous()
+        out = torch.empty(flat.numel(), w.shape[1], device=w.device, dtype=torch.float32)
+        ops.embedding_fwd(w, flat, out)
+        ctx.rows = w.shape[0]
+        ctx.save_for_backward(flat)
+        return out.view(*ids.shape, w.shape[1])
 
-    def __init__(self, cond_num, cond_dim):
+    @staticmethod
+    def backward(ctx, dout):
+        flat, = ctx.saved_tensors
+        d = dout.reshape(flat.numel(), -1).float().contiguous()
+        dweight = torch.empty(ctx.rows, d.shape[1], device=d.device, dtype=torch.float32)
+        ops.embedding_bwd_rows(d, flat, dweight)
+        return None, dweight
+
+
+class Conditions(nn.Module):
+    """Speaker embedding (layers.py:12-60, normalize=False => nn.Embedding);
+    forward(ids) -> ids.shape + (cond_dim,) through vqx_embedding_fwd /
+    vqx_embedding_bwd_rows.  The normalised table (normalize=True) is not built."""
+
+    def __init__(self, cond_num, cond_dim, normalize=False):
         super().__init__()
+        if normalize:
+            raise NotImplementedError("Conditions: normalize=True is not built on the HIP path (no model uses it)")
         self._embedding = nn.Embedding(cond_num, cond_dim)
         self.cond_num = cond_num
+        self.normalize = False
+
+    def forward(self, ids):
+        return _EmbeddingFn.apply(ids, self._embedding.weight)
 
 
 LOG_2PI = math.log(2.0 * math.pi)

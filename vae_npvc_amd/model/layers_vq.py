@@ -6,8 +6,12 @@ reference's buffer names so checkpoints load both ways.
 """
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
+from .. import _lib as L
 from .. import ops
+
+F32 = torch.float32
 
 
 class EMAVectorQuantizer(nn.Module):
@@ -132,8 +136,124 @@ class VectorQuantizer(nn.Module):
         out = out.view(B, T, -1)
         return out.transpose(1, 2).contiguous() if time_last else out
 
+    def forward(self, z, time_last=True, loss_weights=None):
+        """layers_vq.py:79-150 for reduction 'frame_mean' on the HIP kernels:
+        (z_vq, z_qut_loss, z_enc_loss, {'entropy': perplexity}).  z is (B, D, T)
+        ((B, T, D) with time_last=False); z_vq carries the gathered codes and
+        passes its gradient straight through to z; both losses are 0-dim device
+        tensors, and `entropy` stays one until the caller reads it.  With
+        `normalize` the codebook parameter is renormalised in place first
+        (embed_norm(), :96).
+
+        loss_weights=(w_qut, w_enc): returns (z_vq, loss, z_qut_loss,
+        z_enc_loss, detail) where loss = w_qut * z_qut_loss + w_enc * z_enc_loss
+        is the level's one differentiable scalar and the two parts are not
+        differentiable (vqvae2.Model's call: w_qut = 1, w_enc = beta).
+
+        Either way one vqx_vq_plain_bwd_g launch gives dL/dz and dL/dE; the
+        upstream gradients of the scalars are read on the device."""
+        if not self.quantize:  # the reference's early exit (:80-82)
+            tensor_0 = torch.tensor(0.0, dtype=torch.float, device=z.device)
+            return z, tensor_0, tensor_0, tensor_0
+        if self.z_dim not in (64, 128, 256):
+            raise NotImplementedError(f"z_dim {self.z_dim}: the HIP quantizer is built for z_dim 64, 128 or 256")
+        if z.dim() != 3 or z.shape[1 if time_last else 2] != self.z_dim:
+            raise ValueError(f"VectorQuantizer: z {tuple(z.shape)} does not carry {self.z_dim} channels")
+        weights = None if loss_weights is None else (float(loss_weights[0]), float(loss_weights[1]))
+        save = torch.is_grad_enabled() and (z.requires_grad or self.embeddings.requires_grad)
+        z_vq, loss, qut, enc, perp, _ = _QuantizeFn.apply(self.normalize, time_last, weights, save, z,
+                                                          self.embeddings)
+        if weights is None:
+            return z_vq, qut, enc, {"entropy": perp}
+        return z_vq, loss, qut, enc, {"entropy": perp}
+
+    def forward_indices(self, z, time_last=True):
+        """forward's nearest-code indices (B, T) alone, from the same launches
+        (the codebook renormalised in place as forward does)."""
+        with torch.no_grad():
+            return _QuantizeFn.apply(self.normalize, time_last, None, False, z, self.embeddings)[5]
+
     def extra_repr(self):
         return f"{self.z_num}, {self.z_dim}" + (", normalize=True" if self.normalize else "")
+
+
+class _QuantizeFn(torch.autograd.Function):
+    """VectorQuantizer.forward: vqx_vq_normalize (when `normalize`), vqx_vq_forward
+    and vqx_vq_perplexity forward, one vqx_vq_plain_bwd_g backward.  Outputs
+    (z_vq, weighted loss, z_qut_loss, z_enc_loss, perplexity, indices); with
+    `weights` the weighted loss is the differentiable scalar, else the two parts."""
+
+    @staticmethod
+    def forward(ctx, normalize, time_last, weights, save, z, E):
+        if not (z.is_cuda and E.is_cuda):
+            raise L.VqxError("VectorQuantizer.forward runs on the MI355X only (libvqx); move it and z with .cuda()")
+        dev = z.device
+        e = lambda *shape: torch.empty(*shape, device=dev, dtype=F32)  # noqa: E731
+        if time_last:
+            B, D, T = z.shape
+            zf = ops.nct_to_ntc(z.float().contiguous(), e(B * T, D))
+        else:
+            B, T, D = z.shape
+            zf = z.reshape(B * T, D).float().contiguous()
+        N, K = B * T, E.shape[0]
+        if E.dtype != F32 or not E.is_contiguous():
+            raise ValueError("VectorQuantizer: the codebook parameter must be a contiguous f32 tensor")
+        stats = e(3)  # sum ||z_vq - z_norm||^2, sum ||z_norm - z||^2, perplexity
+        counts = ops.zero_(e(1, K * D + K)).view(-1)
+        bsum, bcnt = counts[:K * D].view(K, D), counts[K * D:]
+        if normalize:
+            zn, zl, emb, el = e(N, D), e(N), e(K, D), e(K)
+            ops.vq_normalize(zf, E.detach(), zn, zl, emb, el, e(N // 4 + 2), stats[1:2])
+        else:
+            zn, zl, emb, el = zf, None, E.detach(), None
+        idx = torch.empty(N, device=dev, dtype=torch.int64)
+        zq = e(N, D)
+        ops.vq_forward(zn, emb, idx, zq, None, stats[0:1], None, bsum, bcnt)
+        ops.vq_perplexity(bcnt, N, stats[2:3])
+        qut = stats[0] / N  # frame_mean: the sum over frames and channels / (B*T) (:133-134)
+        enc = (stats[0] + stats[1]) / N if normalize else stats[0] / N
+        loss = weights[0] * qut + weights[1] * enc if weights is not None else qut + enc
+        if time_last:
+            z_vq = ops.ntc_to_nct(zq, e(B, D, T))
+        else:
+            z_vq = zq.view(B, T, D)
+        idx = idx.view(B, T)
+        perp = stats[2].clone()
+        ctx.mark_non_differentiable(idx, perp, *((qut, enc) if weights is not None else (loss,)))
+        ctx.set_materialize_grads(False)
+        if save:
+            ctx.cfg = (normalize, time_last, weights, (B, D, T))
+            ctx.keep = (zf, zn, zl, zq, bsum, bcnt, emb, el)
+        return z_vq, loss, qut, enc, perp, idx
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dzvq, dloss, dqut, denc, dperp, didx):
+        normalize, time_last, weights, (B, D, T) = ctx.cfg
+        zf, zn, zl, zq, bsum, bcnt, emb, el = ctx.keep
+        dev, N = zq.device, B * T
+        if dzvq is None:
+            dzq = None
+        elif time_last:
+            dzq = ops.nct_to_ntc(dzvq.float().contiguous(), torch.empty(N, D, device=dev, dtype=F32))
+        else:
+            dzq = dzvq.reshape(N, D).float().contiguous()
+        if weights is not None:
+            w_qut, w_enc, g_qut, g_enc = weights[0], weights[1], dloss, dloss
+        else:
+            w_qut, w_enc, g_qut, g_enc = 1.0, 1.0, dqut, denc
+        # a scalar nothing depends on: its term is dropped (weight 0), its gradient not read
+        s_qut = 2.0 * w_qut / N if g_qut is not None else 0.0
+        s_enc = 2.0 * w_enc / N if g_enc is not None else 0.0
+        g = [None if t is None else t.detach().float().reshape(1).contiguous() for t in (g_qut, g_enc)]
+        dz, dE = torch.empty(N, D, device=dev, dtype=F32), torch.empty_like(emb)
+        ops.vq_plain_bwd_g(zf, zn, zl, zq, dzq, T, normalize, s_qut, s_enc, g[0], g[1], dz, bsum, bcnt, emb, el, dE)
+        ctx.keep = None
+        if time_last:
+            dz = ops.ntc_to_nct(dz, torch.empty(B, D, T, device=dev, dtype=F32))
+        else:
+            dz = dz.view(B, T, D)
+        return None, None, None, None, dz, dE
 
 
 class Jitter(nn.Module):

@@ -27,12 +27,17 @@ import functools
 import math
 
 import torch
+import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
 from .. import ops
-from .layers import ResSkipBlock, WNConv1d
+from .layers import Conditions, ResSkipBlock, WNConv1d
+from .layers_gst import StyleTokenLayer
+from .layers_vq import Jitter, VectorQuantizer
+from .resample import ResampleConv1d
 from .vqvae import Decoder as _Decoder
+from .vqvae import Encoder as _Encoder
 
 F32 = torch.float32
 _DT = {"fp32": torch.float32, "bf16": torch.bfloat16}
@@ -411,3 +416,402 @@ class Decoder(_Decoder):
         ts = _Plan.tensors(self)
         save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, *levels, *ts))
         return _DecoderFn.apply(self._plan, save, T_levels, x, *levels, *ts)
+
+
+# ------------------------------------------------------------------ encoder
+class _EConv:
+    """One encoder conv of the plan.  Three slots of the flat tensor list from
+    `at`: a stride-1 conv (scale 1) takes (effective weight, bias, None) and
+    returns dL/dw in torch's layout; a strided stage conv (scale s, run folded as
+    model/resample.py does) takes (weight_v | weight, bias, weight_g | None) and
+    returns the parameter gradients of its own weight-norm table."""
+
+    def __init__(self, mod, at):
+        self.mod, self.at = mod, at
+        self.cin, self.cout, self.k = mod.cin, mod.cout, mod.k
+        self.scale = getattr(mod, "scale", 1)
+        self.transposed = False
+        if self.scale == 1:
+            self.dil, self.pad = mod.dilation, mod.padding
+            if 2 * self.pad != (mod.k - 1) * mod.dilation:
+                raise NotImplementedError("asymmetric padding (the output length would change)")
+
+    def tensors(self):
+        m = self.mod
+        if self.scale == 1:
+            return [m.effective_weight(), m.bias, None]
+        return [m.v_param, m.bias, m.g_param]
+
+
+class _EncPlan:
+    """Static description of an Encoder for _EncoderFn (no tensors): per stage
+    its conv and blocks; a block = (stack convs, first GroupNorm slots, skip conv)."""
+
+    def __init__(self, enc):
+        self.dt = _DT[enc.compute_dtype]
+        layers, self.stages, at = list(enc.encode), [], 0
+        bounds = list(enc.stage_index) + [len(layers)]
+        for lo, hi in zip(bounds, bounds[1:]):
+            conv = _EConv(layers[lo], at)
+            at += 3
+            blocks = []
+            for blk in layers[lo + 1:hi - 1]:  # the stage ends with its LeakyReLU
+                convs, gn_at = [], []
+                for cv, gn in zip(blk.convs, blk.norms):
+                    convs.append(_EConv(cv, at))
+                    convs[-1].norm = gn
+                    gn_at.append(at + 3)
+                    at += 5
+                blocks.append((convs, gn_at, _EConv(blk.skip_layer, at)))
+                at += 3
+            self.stages.append((conv, blocks))
+        self.z_proj = _EConv(enc.z_proj, at)
+        self.n_tensors = at + 3
+        self.total_scale = math.prod(cv.scale for cv, _ in self.stages)
+
+    @staticmethod
+    def tensors(enc, plan):
+        out = []
+        for conv, blocks in plan.stages:
+            out += conv.tensors()
+            for convs, _, skip in blocks:
+                for cv in convs:
+                    out += cv.tensors() + [cv.norm.weight, cv.norm.bias]
+                out += skip.tensors()
+        return out + plan.z_proj.tensors()
+
+
+def _down_splits(cv, n, T, dt):
+    tiles = ops.wgrad_tiles(n, T, cv.cout, cv.scale * cv.cin, 3, 1, ops.dt_code(dt))
+    return max(1, min(512 // max(1, tiles), n // 512))
+
+
+class _EncoderFn(torch.autograd.Function):
+    """engine/step.py encoder_fwd / encoder_bwd composed from ops.*, with the
+    second output `feat` = the last stage's LeakyReLU and a gradient into it."""
+
+    @staticmethod
+    def forward(ctx, plan, save, x, *ts):
+        if not x.is_cuda or not all(t.is_cuda for t in ts if t is not None):
+            raise L.VqxError("vqvae2.Encoder runs on the MI355X only (libvqx); move it and its input with .cuda()")
+        dev, dt = x.device, plan.dt
+        B, _, T = x.shape
+        ts = [None if t is None else t.detach().float() for t in ts]
+        e = functools.partial(torch.empty, device=dev)
+        inp = ops.nct_to_ntc(x.float().contiguous(), e(B * T, x.shape[1], dtype=dt))
+        gn_part = e(B * 2 * 24, dtype=F32)
+        wp, saved, T_in = {}, [], T
+        for conv, blocks in plan.stages:
+            s, C = conv.scale, conv.cout
+            Ts = T_in // s
+            N = B * Ts
+            # every GEMM producing c_j also writes a_j = LeakyReLU(c_j), the operand of the
+            # next conv stack / stage conv / z_proj (vqvae2.py:224, layers.py:152)
+            c, a = e(N, C, dtype=dt), e(N, C, dtype=dt)
+            if s == 1:
+                w = wp[conv.at] = _pack(ts[conv.at], False, dt)
+                _fwd(conv, inp, w, c, T_in, bias=ts[conv.at + 1], act=L.PRO_LRELU, y2=a)
+            else:  # folded: s frames of cin channels as one frame of s*cin, 3 taps
+                w, norm = e(C, 3 * s * conv.cin, dtype=dt), e(C, dtype=F32)
+                ops.weight_norm_fwd(conv.mod._table(w, norm))
+                wp[conv.at] = (w, norm)
+                ops.conv_fwd(inp.view(N, s * conv.cin), w, c, T=Ts, cin=s * conv.cin, cout=C, ntaps=3, pad=1,
+                             bias=ts[conv.at + 1], act=L.PRO_LRELU, y2=a)
+            fuse = Ts % 128 == 0 and C % 128 == 0  # GroupNorm statistics from the GEMM's epilogue tiles
+            cs, acts, per_block = [c], [a], []
+            for convs, gn_at, skip in blocks:
+                src, hs, mrs, gs, gkw = acts[-1], [], [], [], {}
+                for l, (cv, ag) in enumerate(zip(convs, gn_at)):
+                    last = l == len(convs) - 1
+                    w = wp[cv.at] = _pack(ts[cv.at], False, dt)
+                    h, mr = e(N, C, dtype=dt), e(B, 2, dtype=F32)
+                    if fuse:
+                        gst = e((N // 128) * (C // 128) * 4, dtype=F32)
+                        _fwd(cv, src, w, h, Ts, bias=ts[cv.at + 1], gn_stats=gst, gn_groups=1)
+                        if last:
+                            gkw = dict(gn_tiles=gst)  # merged inside the skip GEMM
+                        else:
+                            ops.gn_finalize_tiles(gst, N, Ts, C, 1, mr)
+                    else:
+                        _fwd(cv, src, w, h, Ts, bias=ts[cv.at + 1])
+                        ops.groupnorm_stats(h, Ts, 1, gn_part, mr)
+                    if not last:  # LeakyReLU(GN(h)): the next conv's operand (layers.py:156-161)
+                        g = e(N, C, dtype=dt)
+                        ops.gn_lrelu_fwd(h, g, Ts, mr, ts[ag], ts[ag + 1])
+                        gs.append(g)
+                        src = g
+                    hs.append(h)
+                    mrs.append(mr)
+                w = wp[skip.at] = _pack(ts[skip.at], False, dt)
+                c, a = e(N, C, dtype=dt), e(N, C, dtype=dt)
+                _fwd(skip, cs[-1], w, c, Ts, bias=ts[skip.at + 1], gn_h=hs[-1], gn_mr=mrs[-1], gn_gamma=ts[gn_at[-1]],
+                     gn_beta=ts[gn_at[-1] + 1], act=L.PRO_LRELU, y2=a, **gkw)
+                cs.append(c)
+                acts.append(a)
+                per_block.append((hs, mrs, gs))
+            saved.append((inp, T_in, Ts, cs, acts, per_block))
+            inp, T_in = acts[-1], Ts
+        zp = plan.z_proj
+        w = wp[zp.at] = _pack(ts[zp.at], False, dt)
+        z = e(B * T_in, zp.cout, dtype=F32)
+        _fwd(zp, inp, w, z, T_in, bias=ts[zp.at + 1], out_f32=True)
+        ctx.set_materialize_grads(False)
+        if save:
+            ctx.plan, ctx.B = plan, B
+            ctx.keep = (saved, wp, ts)
+        return _to_nct(z, B, T_in), _to_nct(inp, B, T_in)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz, dfeat):
+        plan, B = ctx.plan, ctx.B
+        saved, wp, ts = ctx.keep
+        ctx.keep = None
+        grads = [None] * plan.n_tensors
+        if dz is None and dfeat is None:
+            return (None, None, None, *grads)
+        dev, dt = (dz if dz is not None else dfeat).device, plan.dt
+        e = functools.partial(torch.empty, device=dev)
+        Cmax = max(conv.cout for conv, _ in plan.stages)
+        cs_part = e(64 * max(Cmax, plan.z_proj.cout, 1024), dtype=F32)
+        gnb_part = e(B * 64 * 2, dtype=F32)
+        # the gradient at the last activation a: lrelu'(a) * (W_proj^T dz + dfeat).  The GEMM
+        # epilogue applies MASK before RES, so dfeat arrives already masked (vqx_nct_to_ntc_lrelu_bwd)
+        _, _, Ts, _, acts, _ = saved[-1]
+        a_last, N = acts[-1], B * Ts
+        masked = None
+        if dfeat is not None:
+            masked = ops.nct_to_ntc_lrelu_bwd(dfeat.float().contiguous(), a_last, 0.2, e(N, a_last.shape[1], dtype=dt))
+        if dz is not None:
+            zp = plan.z_proj
+            dzr = ops.nct_to_ntc(dz.float().contiguous(), e(N, zp.cout, dtype=dt))
+            grads[zp.at + 1] = _colsum(dzr, cs_part)
+            grads[zp.at] = _wgrad(zp, dzr, a_last, Ts)
+            cur = e(N, zp.cin, dtype=dt)
+            _dgrad(zp, dzr, wp[zp.at], cur, Ts, mask=a_last, mask_slope=0.2,
+                   **({} if masked is None else dict(res=masked)))
+        else:
+            cur = masked
+        dx = None
+        for si in reversed(range(len(plan.stages))):
+            conv, blocks = plan.stages[si]
+            inp, T_in, Ts, cs, acts, per_block = saved[si]
+            N, C = B * Ts, conv.cout
+            for j in reversed(range(len(blocks))):
+                convs, gn_at, skip = blocks[j]
+                hs, mrs, gs = per_block[j]
+                # cur = dL/dc_{j+1}, the gradient w.r.t. block j's output GN(h_L) + skip(c_j)
+                dy, tmp = cur, None
+                for l in reversed(range(len(convs))):
+                    cv, ag = convs[l], gn_at[l]
+                    dh = e(N, C, dtype=dt)
+                    cs_b, dgam_b, dbet_b = (e(B, C, dtype=F32) for _ in range(3))
+                    ops.gn_bwd(dy, hs[l], dh, Ts, 1, False, mrs[l], ts[ag], ts[ag + 1], gnb_part, cs_b, dgam_b, dbet_b)
+                    grads[cv.at + 1] = _colsum(cs_b, cs_part)
+                    grads[ag], grads[ag + 1] = _colsum(dgam_b, cs_part), _colsum(dbet_b, cs_part)
+                    src = acts[j] if l == 0 else gs[l - 1]
+                    grads[cv.at] = _wgrad(cv, dh, src, Ts)
+                    # into LeakyReLU(.): its derivative from the sign of the stored output
+                    dy = tmp = e(N, C, dtype=dt)
+                    _dgrad(cv, dh, wp[cv.at], dy, Ts, mask=src, mask_slope=0.2)
+                # the skip conv last, adding the stack's data gradient
+                grads[skip.at + 1] = _colsum(cur, cs_part)
+                grads[skip.at] = _wgrad(skip, cur, cs[j], Ts)
+                nxt = e(N, C, dtype=dt)
+                _dgrad(skip, cur, wp[skip.at], nxt, Ts, res=tmp)
+                cur = nxt
+            # cur = dL/dc_0 of the stage (the stage conv's output)
+            grads[conv.at + 1] = _colsum(cur, cs_part)
+            want_dx = si > 0 or ctx.needs_input_grad[2]
+            prev_a = saved[si - 1][4][-1] if si > 0 else None
+            mask = {} if si == 0 else dict(mask=prev_a, mask_slope=0.2)
+            s = conv.scale
+            if s == 1:
+                grads[conv.at] = _wgrad(conv, cur, inp, T_in)
+                if want_dx:
+                    nxt = e(B * T_in, conv.cin, dtype=dt if si else F32)
+                    _dgrad(conv, cur, wp[conv.at], nxt, T_in, **(mask if si else dict(out_f32=True)))
+            else:
+                w, norm = wp[conv.at]
+                fold = s * conv.cin
+                splits = _down_splits(conv, N, Ts, dt)
+                slabs = e(splits, C, 3 * fold, dtype=F32)
+                ops.conv_wgrad(cur, inp.view(N, fold), slabs, T=Ts, r_dim=C, c_dim=fold, ntaps=3, pad=1, shift_sign=1,
+                               splits=splits)
+                dv = torch.empty_like(ts[conv.at])
+                dg = torch.empty_like(ts[conv.at + 2]) if ts[conv.at + 2] is not None else None
+                ops.weight_norm_bwd(conv.mod._table(w, norm, dv=dv, dg=dg, slabs=slabs, splits=splits))
+                grads[conv.at], grads[conv.at + 2] = dv, dg
+                if want_dx:
+                    nxt = e(B * T_in, conv.cin, dtype=dt if si else F32)
+                    if si:
+                        mask = dict(mask=prev_a.view(N, fold), mask_slope=0.2)
+                    ops.conv_dgrad(cur, w, nxt.view(N, fold), T=Ts, cin=C, cout=fold, ntaps=3, pad=1,
+                                   **(mask if si else dict(out_f32=True)))
+            if si:
+                cur = nxt
+            elif want_dx:
+                dx = _to_nct(nxt, B, T_in)
+        return (None, None, dx, *grads)
+
+
+class Encoder(_Encoder):
+    """vqvae2.py:175-271 with `compute_dtype: fp32|bf16`: forward(x (B, C_in, T))
+    -> (z, feat), z = z_proj(feat) (B, z_channels, T'), feat the last stage's
+    LeakyReLU output (B, out_channels[-1], T'), T' = T / prod(downsample_scales).
+    The reference's module tree: `encode` (without the projection) and `z_proj`."""
+
+    def __init__(self, *args, compute_dtype="fp32", **kw):
+        if compute_dtype not in _DT:
+            raise ValueError(f"compute_dtype {compute_dtype!r} is not fp32 or bf16")
+        super().__init__(*args, **kw)
+        layers = list(self.encode)
+        self.encode = nn.Sequential(*layers[:-1])
+        self.z_proj = layers[-1]
+        self.compute_dtype = compute_dtype
+        self._plan = None
+
+    def forward(self, x):
+        if x.dim() != 3 or x.shape[1] != self.in_ch:
+            raise ValueError(f"vqvae2.Encoder: x {tuple(x.shape)} is not (B, {self.in_ch}, T)")
+        if self._plan is None:
+            self._plan = _EncPlan(self)
+        plan = self._plan
+        if x.shape[2] % plan.total_scale:
+            raise ValueError(f"vqvae2.Encoder: T = {x.shape[2]} is not a multiple of the down-sampling "
+                             f"{plan.total_scale}")
+        ts = _EncPlan.tensors(self, plan)
+        save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, *ts) if t is not None)
+        return _EncoderFn.apply(plan, save, x, *ts)
+
+
+# ------------------------------------------------------------------ model
+class _LogLossFn(torch.autograd.Function):
+    """log_loss(xhat, x) (layers.py:283-296, 'frame_mean') as vqx_logloss_fwd_bwd:
+    the launch that sums the loss also writes d loss / d xhat; the backward is
+    its layout change with the upstream gradient folded in (vqx_ntc_to_nct_scale)."""
+
+    @staticmethod
+    def forward(ctx, xhat, x):
+        B, C, T = x.shape
+        rows = _to_rows(xhat)
+        loss = torch.empty(1, device=x.device, dtype=F32)
+        dxhat = torch.empty_like(rows)
+        ops.logloss_fwd_bwd(x, rows, 1.0 / (B * T), dxhat, loss, torch.empty(1024, device=x.device, dtype=F32))
+        ctx.dims = (B, T)
+        ctx.save_for_backward(dxhat)
+        return loss.view(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        dxhat, = ctx.saved_tensors
+        B, T = ctx.dims
+        dx = torch.empty(B, dxhat.shape[1], T, device=dxhat.device, dtype=F32)
+        return ops.ntc_to_nct_scale(dxhat, g.detach().float().reshape(1).contiguous(), dx), None
+
+
+class Model(nn.Module):
+    """The reference's hierarchical `Model` (vqvae2.py:11-172) for
+    `model_type: vae_npvc_amd.model.vqvae2`: `Model(arch)` with the keys levels,
+    use_gst, use_ema, beta, y_num, y_dim, jitter_p, encoder.{i}, decoder.{i},
+    quantizer.{i} (+ compute_dtype: fp32|bf16), the reference's module tree
+    (encoders, quantizers, decoders, embeds, jitter) and state_dict keys.
+
+    forward((x, y_idx)) restates vqvae2.py:74-127 as a composition of the HIP
+    modules under torch autograd, so the reference's trainer (model(input),
+    loss.backward(), a stock optimizer) runs it unchanged.  No stretched tensor
+    is built for conditioning: each decoder receives its low-rate levels as a
+    list; only the input of decoders[0] goes through upsample_cat.  The loss
+    dict comes from one readback of the packed scalars at the end.
+
+    Not built (NotImplementedError): use_ema: true (EMAVectorQuantizer.forward
+    inside the hierarchy), jitter_p != 0, and encode / decode / infer, whose
+    reference versions refer to members the class does not have."""
+
+    def __init__(self, arch):
+        super().__init__()
+        levels = arch.get("levels", 3)
+        use_gst = arch.get("use_gst", True)
+        use_ema = arch.get("use_ema", True)
+        jitter_p = arch.get("jitter_p", 0.0)
+        if use_ema and (levels > 1 or not use_gst):
+            raise NotImplementedError("vqvae2.Model: use_ema: true needs EMAVectorQuantizer.forward, which is not "
+                                      "built for the hierarchical model; set use_ema: false (the vae2 recipe's value)")
+        if jitter_p != 0:
+            raise NotImplementedError(f"vqvae2.Model: jitter_p {jitter_p} is not built for the hierarchical model "
+                                      "(the vae2 recipe uses 0)")
+        dtype = arch.get("compute_dtype", "fp32")
+        encoders, quantizers, decoders = [], [], []
+        for i in range(levels):
+            encoders.append(Encoder(**arch[f"encoder.{i}"], compute_dtype=dtype))
+            decoders.append(Decoder(**arch[f"decoder.{i}"], compute_dtype=dtype))
+            Quantizer = StyleTokenLayer if use_gst and i == levels - 1 else VectorQuantizer
+            quantizers.append(Quantizer(**arch[f"quantizer.{i}"]))
+        self.encoders = nn.ModuleList(encoders)
+        self.quantizers = nn.ModuleList(quantizers)
+        self.decoders = nn.ModuleList(decoders)
+        self.embeds = Conditions(arch.get("y_num", 10), arch.get("y_dim", 128), normalize=False)
+        self.jitter = Jitter(probability=jitter_p)
+        self.beta = arch.get("beta", 0.01)
+        self.levels, self.use_gst, self.use_ema = levels, use_gst, use_ema
+        self.compute_dtype = dtype
+
+    def forward(self, input):
+        """(x (B, mel, T), y_idx (B, 1)) -> (xhat (B, mel, T), loss, loss dict)."""
+        x, y_idx = input
+        if not x.is_cuda:
+            raise L.VqxError("vqvae2.Model runs on the MI355X only (libvqx); move it and its inputs with .cuda()")
+        x = x.float().contiguous()
+        y = self.embeds(y_idx[..., :1]).transpose(1, 2)  # (B, y_dim, 1)
+        # hierarchical encode: level i reads level i-1's feature map
+        z_levels, feat = [], x
+        for enc in self.encoders:
+            z, feat = enc(feat)
+            z_levels.append(z)
+        # quantize and decode from the top; z_vqs holds the quantized levels at their own rates, top first
+        z_vqs, level_losses, enc_losses, scalars = [], [], [], []
+        z = z_levels.pop()
+        for i in reversed(range(self.levels)):
+            if self.use_gst and i == self.levels - 1:
+                z_vq = self.quantizers[i].pool_forward(z).unsqueeze(-1)
+            else:
+                z_vq, lvl, _, z_enc, detail = self.quantizers[i](z, loss_weights=(1.0, self.beta))
+                level_losses.append(lvl)
+                enc_losses.append(z_enc)
+                scalars += [detail["entropy"], z_enc]
+            z_vqs.append(z_vq)
+            if i > 0:
+                z = self.decoders[i]((z_levels.pop(), list(z_vqs)))
+        xhat = self.decoders[0]((upsample_cat(z_vqs, x.shape[2]), [y]))
+        x_loss = _LogLossFn.apply(xhat, x)
+        loss = x_loss
+        for lvl in level_losses:
+            loss = loss + lvl
+        vq = enc_losses[0]
+        for t in enc_losses[1:]:
+            vq = vq + t
+        host = torch.stack([loss.detach(), vq, x_loss.detach(), *scalars]).tolist()  # the step's one readback
+        losses = {"Total": host[0], "VQ loss": host[1], "X like": host[2]}
+        for k in range(len(level_losses)):
+            losses[f"entropy.{k}"] = host[3 + 2 * k]
+            losses[f"quanti_err.{k}"] = host[4 + 2 * k]
+        return xhat, loss, losses
+
+    def encode(self, input):
+        raise NotImplementedError("vqvae2.Model.encode: the reference's version reads self.encoder and self.quantizer, "
+                                  "which the hierarchical model does not have (vqvae2.py:49-56); no semantics to restate")
+
+    def decode(self, input):
+        raise NotImplementedError("vqvae2.Model.decode: the reference's version reads self.quantizer and self.decoder, "
+                                  "which the hierarchical model does not have (vqvae2.py:59-64); no semantics to restate")
+
+    def infer(self, input):
+        raise NotImplementedError("vqvae2.Model.infer: built on encode / decode, which the reference leaves undefined "
+                                  "for the hierarchical model (vqvae2.py:67-71)")
+
+    def remove_weight_norm(self):
+        """vqvae2.py:146-156: bake w = g*v/||v|| into a plain `weight` on every conv that has weight norm."""
+        for m in self.modules():
+            if isinstance(m, (WNConv1d, ResampleConv1d)) and m.has_weight_norm:
+                m.remove_weight_norm()

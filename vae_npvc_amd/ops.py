@@ -911,6 +911,20 @@ def vq_plain_bwd(z, z_norm, z_len, zq, dzq, src_t, T, normalize, beta, scale, dz
          ptr(e_len), emb.shape[0], ptr(dE), stream_ptr())
 
 
+def vq_plain_bwd_g(z, z_norm, z_len, zq, dzq, T, normalize, s_qut, s_enc, g_qut, g_enc, dz, bsum, bcnt, emb, e_len,
+                   dE):
+    """vq_plain_bwd with the weights of z_qut / z_enc given apart (s_qut = scale,
+    s_enc = beta * scale) and their upstream gradients as device scalars (f32,
+    one element each; None = 1): no readback (vqx_vq_plain_bwd_g)."""
+    _check_cuda(z_norm, zq, dz, bsum, bcnt, emb, dE)
+    for g in (g_qut, g_enc):
+        if g is not None and (not g.is_cuda or g.dtype != torch.float32 or g.numel() != 1):
+            raise ValueError("vq_plain_bwd_g: an upstream gradient must be a one-element f32 device tensor")
+    call("vqx_vq_plain_bwd_g", ptr(z), ptr(z_norm), ptr(z_len), ptr(zq), ptr(dzq), T, zq.shape[0], zq.shape[1],
+         int(normalize), s_qut, s_enc, ptr(g_qut), ptr(g_enc), ptr(dz), dt_code(dz.dtype), ptr(bsum), ptr(bcnt),
+         ptr(emb), ptr(e_len), emb.shape[0], ptr(dE), stream_ptr())
+
+
 GST_PARAMS = ("gst_embs", "wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo")  # vqx_gst_args order
 
 
@@ -1021,6 +1035,36 @@ def upsample_cat_bwd(dlevels, B, T, dout):
     _rows(dout, dout.shape[0], dout.stride(0), sum(z.shape[1] for z in dlevels), "upsample_cat_bwd dout")
     call("vqx_upsample_cat_bwd", arr, len(dlevels), B, T, ptr(dout), dout.stride(0), dt_code(dout.dtype), stream_ptr())
     return dlevels
+
+
+def nct_to_ntc_lrelu_bwd(g_nct, a, slope, dst):
+    """dst[b*T + t, c] = g_nct[b, c, t] * (a[b*T + t, c] > 0 ? 1 : slope)
+    (vqx_nct_to_ntc_lrelu_bwd): the f32 (B, C, T) gradient into a LeakyReLU's
+    output, through it, as frame-major rows in dst's dtype; a, dst [B*T, >= C]."""
+    _check_cuda(g_nct, a, dst)
+    B, C, T = g_nct.shape
+    if g_nct.dtype != torch.float32 or not g_nct.is_contiguous():
+        raise ValueError("nct_to_ntc_lrelu_bwd: g must be a contiguous f32 (B, C, T) tensor")
+    for t, what in ((a, "a"), (dst, "dst")):
+        if t.dim() != 2 or t.shape[0] != B * T or t.shape[1] < C or t.stride(1) != 1:
+            raise ValueError(f"nct_to_ntc_lrelu_bwd: {what} must be [{B * T}, >= {C}] rows with unit column stride")
+        _rows(t, B * T, t.stride(0), C, f"nct_to_ntc_lrelu_bwd {what}")
+    call("vqx_nct_to_ntc_lrelu_bwd", ptr(g_nct), B, C, T, ptr(a), a.stride(0), dt_code(a.dtype), slope, ptr(dst),
+         dst.stride(0), dt_code(dst.dtype), stream_ptr())
+    return dst
+
+
+def ntc_to_nct_scale(y, g, x_nct):
+    """x_nct[b, c, t] = y[b*T + t, c] * g[0] (vqx_ntc_to_nct_scale): f32 rows to (B, C, T)
+    times a one-element f32 device tensor."""
+    _check_cuda(y, g, x_nct)
+    B, C, T = x_nct.shape
+    if y.dtype != torch.float32 or g.dtype != torch.float32 or x_nct.dtype != torch.float32 or g.numel() != 1 \
+            or not x_nct.is_contiguous() or y.dim() != 2 or y.shape[0] != B * T or y.shape[1] < C or y.stride(1) != 1:
+        raise ValueError(f"ntc_to_nct_scale: f32 y [{B * T}, >= {C}] rows, a one-element f32 g, contiguous f32 x")
+    _rows(y, B * T, y.stride(0), C, "ntc_to_nct_scale y")
+    call("vqx_ntc_to_nct_scale", ptr(y), y.stride(0), B, C, T, ptr(g), ptr(x_nct), stream_ptr())
+    return x_nct
 
 
 def cu_masked_stream(reserve_cus):
