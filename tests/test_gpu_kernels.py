@@ -1556,3 +1556,139 @@ def test_ema_update_close_equals_the_separate_launches(n_vq, rows):
     assert torch.equal(ca, cb) and torch.equal(cb, sb)
     assert np.array_equal(ga, gb) and np.array_equal(gb, sb.cpu().numpy())
     assert za == 0.0 and zb == 0.0
+
+
+# ---- small ops without another direct test: each against stock torch.  Outputs are NaN-filled
+# with one more row of NaN behind them; fp32 results may be 4 x err32 from float64 (err32: stock
+# torch's float32 CPU error of the same expression in the same norm), bf16 results 2^-8 more.
+
+def _guarded(shape, dtype=torch.float32):
+    """(whole, view): a NaN tensor of `shape` and one more sentinel row behind it."""
+    whole = torch.full((shape[0] + 1,) + tuple(shape[1:]), float("nan"), device=DEV, dtype=dtype)
+    return whole, whole[:shape[0]]
+
+
+def _sentinel_ok(whole):
+    return bool(torch.isnan(whole[-1:]).all())
+
+
+def _jitter_map(T, gen):
+    """A Jitter source map (layers_vq.py:353-379): a third of the frames read a neighbour, both ends among them."""
+    src = torch.arange(T, dtype=torch.int32)
+    for t in (torch.randperm(T - 2, generator=gen)[:T // 3 - 2] + 1).tolist():
+        src[t] = t + (1 if torch.rand(1, generator=gen).item() < 0.5 else -1)
+    src[0], src[T - 1] = 1, T - 2
+    return src
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("B,T,C,ld", [(3, 50, 96, 96), (2, 33, 64, 80)])
+def test_gn_lrelu_fwd_matches_torch(dtype, B, T, C, ld):
+    """vqx_gn_lrelu_fwd with vqx_groupnorm_stats' statistics against
+    leaky_relu(group_norm(x.double(), 1, gamma, beta), 0.2); rows of stride
+    ld >= C whose padding columns stay untouched, B*T*C/V chunks that do not
+    fill the last workgroup.  Measured error / bound on the MI355X: 0.32
+    (fp32), 0.43 (bf16)."""
+    ops = _ops()
+    gen = torch.Generator(device="cpu").manual_seed(300 + C)
+    x = (torch.randn(B, T, C, generator=gen) * 1.5 + 0.3).to(dtype)
+    gamma, beta = torch.randn(C, generator=gen), torch.randn(C, generator=gen)
+    h = torch.zeros(B * T, ld, device=DEV, dtype=dtype)
+    h[:, :C] = x.view(B * T, C).to(DEV)
+    whole, g = _guarded((B * T, ld), dtype)
+    mr = torch.empty(B, 2, device=DEV)
+    ops.groupnorm_stats(h[:, :C], T, 1, torch.empty(B * 24, device=DEV), mr)
+    ops.gn_lrelu_fwd(h[:, :C], g[:, :C], T, mr, gamma.to(DEV), beta.to(DEV))
+    torch.cuda.synchronize()
+
+    def ref(dt):
+        y = F.leaky_relu(F.group_norm(x.to(dt).transpose(1, 2), 1, gamma.to(dt), beta.to(dt), eps=1e-5), 0.2)
+        return y.transpose(1, 2).reshape(B * T, C)
+
+    r64 = ref(torch.float64)
+    bound = 4 * relerr(ref(torch.float32), r64) + (2.0 ** -8 if dtype == torch.bfloat16 else 0.0)
+    e = relerr(g[:, :C], r64)
+    print(f"gn_lrelu_fwd {dtype} C={C}: err {e:.3g} bound {bound:.3g} ratio {e / bound:.3f}")
+    assert _sentinel_ok(whole) and not bool(torch.isnan(g[:, :C]).any())
+    assert bool(torch.isnan(g[:, C:]).all())
+    assert e <= bound, (e, bound)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_time_gather_equals_indexing(dtype):
+    """vqx_time_gather: y[b][t] = x[b][src_t[t]] for a jitter map (a third of
+    37 frames moved, t = 0 and T - 1 among them), exactly."""
+    ops = _ops()
+    B, T, C = 3, 37, 80
+    gen = torch.Generator(device="cpu").manual_seed(310)
+    x = torch.randn(B * T, C, generator=gen).to(dtype)
+    src = _jitter_map(T, gen)
+    whole, y = _guarded((B * T, C), dtype)
+    ops.time_gather(x.to(DEV), y, B, T, src.to(DEV))
+    torch.cuda.synchronize()
+    assert _sentinel_ok(whole)
+    assert torch.equal(y.cpu().view(B, T, C), x.view(B, T, C)[:, src.long()])
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("B,C,T", [(2, 80, 37), (1, 33, 65)])
+def test_ntc_to_nct_and_its_scaled_form(dtype, B, C, T):
+    """vqx_ntc_to_nct (rows of stride ld > C, ragged 32 x 32 tiles in both
+    directions) is an exact copy into f32 (B, C, T) (of the upcast for bf16
+    rows); vqx_ntc_to_nct_scale (f32 rows only) is y^T * g[0] as one f32
+    product, exactly."""
+    ops = _ops()
+    ld = C + 7 if dtype == torch.float32 else C + 8
+    gen = torch.Generator(device="cpu").manual_seed(320 + C)
+    y = torch.randn(B * T, ld, generator=gen).to(dtype)
+    want = y[:, :C].float().view(B, T, C).transpose(1, 2).contiguous()
+    whole, x = _guarded((B, C, T))
+    ops.ntc_to_nct(y.to(DEV)[:, :C], x)
+    torch.cuda.synchronize()
+    assert _sentinel_ok(whole) and torch.equal(x.cpu(), want)
+    if dtype == torch.float32:
+        g = torch.tensor([0.7312], dtype=torch.float32)
+        whole, x = _guarded((B, C, T))
+        ops.ntc_to_nct_scale(y.to(DEV)[:, :C], g.to(DEV), x)
+        torch.cuda.synchronize()
+        assert _sentinel_ok(whole) and torch.equal(x.cpu(), want * g)
+
+
+@pytest.mark.parametrize("B,I,O", [(5, 70, 100), (64, 128, 1024)])
+def test_linear_f32_and_its_backward_match_float64(B, I, O):
+    """vqx_linear_f32 (out = c W^T + bias) and vqx_linear_bwd_f32 (dW += dout^T c,
+    dc += dout W: both accumulate, so they start from random values) against
+    float64; dW alone and dc alone (NULL for the other) have the bits of the
+    joint call.  Measured error / bound on the MI355X: out 0.27, dW 0.25,
+    dc 0.21."""
+    ops = _ops()
+    gen = torch.Generator(device="cpu").manual_seed(330 + B)
+    c, W = torch.randn(B, I, generator=gen), torch.randn(O, I, generator=gen) / I ** 0.5
+    bias, dout = torch.randn(O, generator=gen), torch.randn(B, O, generator=gen)
+    dW0, dc0 = torch.randn(O, I, generator=gen), torch.randn(B, I, generator=gen)
+
+    def ref(dt):
+        c_, W_, b_, d_ = c.to(dt), W.to(dt), bias.to(dt), dout.to(dt)
+        return dict(out=F.linear(c_, W_, b_), dW=dW0.to(dt) + d_.t() @ c_, dc=dc0.to(dt) + d_ @ W_)
+
+    r64, r32 = ref(torch.float64), ref(torch.float32)
+    cd, Wd, dd = c.to(DEV), W.to(DEV), dout.to(DEV)
+    out_w, out = _guarded((B, O))
+    ops.linear_f32(cd, Wd, bias.to(DEV), out)
+    got = {"out": (out_w, out)}
+    for name, base in (("dW", dW0), ("dc", dc0)):
+        for variant in ("both", "alone"):
+            got[name, variant] = _guarded(base.shape)
+            got[name, variant][1].copy_(base.to(DEV))
+    ops.linear_bwd_f32(dd, cd, Wd, dW=got["dW", "both"][1], dc=got["dc", "both"][1])
+    ops.linear_bwd_f32(dd, cd, Wd, dW=got["dW", "alone"][1])
+    ops.linear_bwd_f32(dd, cd, Wd, dc=got["dc", "alone"][1])
+    torch.cuda.synchronize()
+    for key, (whole, view) in got.items():
+        assert _sentinel_ok(whole) and not bool(torch.isnan(view).any()), key
+    for name in ("dW", "dc"):
+        assert torch.equal(got[name, "both"][1], got[name, "alone"][1]), name
+    for name, view in (("out", out), ("dW", got["dW", "both"][1]), ("dc", got["dc", "both"][1])):
+        e, bound = relerr(view, r64[name]), 4 * relerr(r32[name], r64[name])
+        print(f"linear_f32 B={B} {name}: err {e:.3g} bound {bound:.3g} ratio {e / bound:.3f}")
+        assert e <= bound, (name, e, bound)
