@@ -629,6 +629,40 @@ int vqx_radam_step(float* p, const float* g, float* m, float* v, int64_t n, cons
                    const float* sumsq, float max_norm, vqx_stream_t stream);
 
 /*
+ * Multi-tensor clip + Adam / RAdam (ABI 130, additive): for a model whose
+ * gradients are separate tensors with addresses that change every step (torch
+ * autograd over vqvae2.Model), while p, m and v stay flat.  grads, numel and
+ * offset are HOST arrays of n entries; the device pointers in grads may be
+ * NULL (a parameter without a gradient) and must be 4-B aligned.  Any n is
+ * accepted: the tensors go to the device in groups of at most
+ * VQX_MULTI_MAX_TENSORS per launch, pointers and lengths by value in the
+ * kernel arguments, so nothing is uploaded, allocated or synchronised.
+ * multi_chunks: *out = sum ceil(numel[i] / VQX_MULTI_CHUNK) (host only).
+ * multi_sq_norm: one partial sum of g^2 per VQX_MULTI_CHUNK-element chunk of
+ *   every tensor, in tensor order, so the position of every partial follows
+ *   from numel alone; a NULL gradient writes zeros for its chunks.  n_partials
+ *   must equal multi_chunks.  Deterministic, and the same bits for a 16-B
+ *   aligned gradient and one that is not.  Finish with vqx_sq_norm_finish_adam
+ *   or vqx_sq_norm_finish (+ vqx_radam_hyper), no ranges.
+ * multi_adam_step: tensor i updates p, m, v[offset[i], offset[i] + numel[i])
+ *   from grads[i]; kind 0 is vqx_adam_step's element update, 1 vqx_radam_step's,
+ *   bit for bit what those give on a gathered copy.  A NULL gradient leaves
+ *   that tensor's p, m and v untouched (torch.optim.Adam skips a parameter
+ *   without a gradient).  The ranges must be in increasing order, disjoint and
+ *   inside [0, n_flat).  16-B accesses for a tensor whose p + offset,
+ *   m + offset, v + offset and gradient are all 16-B aligned, single elements
+ *   otherwise.
+ */
+#define VQX_MULTI_MAX_TENSORS 128
+#define VQX_MULTI_CHUNK 4096
+int vqx_multi_chunks(const int64_t* numel, int32_t n, int64_t* out);
+int vqx_multi_sq_norm(const float* const* grads, const int64_t* numel, int32_t n, float* partials,
+                      int64_t n_partials, vqx_stream_t stream);
+int vqx_multi_adam_step(float* p, float* m, float* v, int64_t n_flat, const int64_t* offset,
+                        const int64_t* numel, const float* const* grads, int32_t n, const float* hyper,
+                        const float* sumsq, float max_norm, int32_t kind, vqx_stream_t stream);
+
+/*
  * Straight-through VectorQuantizer (use_ema: false; layers_vq.py:9-163,
  * reduction 'frame_mean', target_norm 1.0, z_dim 64, 128 or 256).
  * vqx_vq_normalize (embed_norm: true): the codebook parameter E [K][D] is

@@ -195,6 +195,10 @@ _SIGS = {
     "vqx_adam_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p],
     "vqx_radam_hyper": [c_void_p, c_double, c_double, c_int32, c_double, c_double, c_double, c_void_p, c_void_p],
     "vqx_radam_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p],
+    "vqx_multi_chunks": [c_void_p, c_int32, ctypes.POINTER(c_int64)],
+    "vqx_multi_sq_norm": [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p],
+    "vqx_multi_adam_step": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                            c_void_p, c_float, c_int32, c_void_p],
     "vqx_gst_workspace": [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, ctypes.POINTER(c_int64)],
     "vqx_gst_fwd": [ctypes.POINTER(GstArgs), c_void_p],
     "vqx_gst_bwd": [ctypes.POINTER(GstArgs), c_void_p],

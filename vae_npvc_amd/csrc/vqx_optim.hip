@@ -1,5 +1,6 @@
-// The global gradient norm and the optimizers (gfx950): Adam, RAdam and Adam
-// fused with the next forward's weight-norm preparation.
+// The global gradient norm and the optimizers (gfx950): Adam, RAdam, Adam
+// fused with the next forward's weight-norm preparation, and the multi-tensor
+// pair for gradients that are separate tensors (flat p, m, v).
 #include "vqx_common.h"
 #include "vqx_wn_pack.h"
 #include <math.h>
@@ -143,26 +144,42 @@ __global__ void radam_hyper_kernel(int64_t* __restrict__ step, double lr0, doubl
   hyper[8] = (float)eps;
 }
 
+// one RAdam element update (radam.py:41-42, 64-71), every operation rounded on its own
+struct RAdamHyper {
+  float coef, val, b1, omb1, b2, omb2, eps;
+  bool rect;
+};
+__device__ __forceinline__ RAdamHyper radam_hyper_load(const float* hyper, const float* sumsq, float max_norm) {
+  RAdamHyper h;
+  h.coef = 1.f;
+  if (max_norm > 0.f && sumsq) {
+    const float tn = sqrtf(sumsq[0]);
+    h.coef = max_norm / (tn + 1e-6f);
+    h.coef = h.coef < 1.f ? h.coef : 1.f;
+  }
+  h.val = hyper[1];
+  h.rect = hyper[2] != 0.f;
+  h.b1 = hyper[4]; h.omb1 = hyper[5]; h.b2 = hyper[6]; h.omb2 = hyper[7]; h.eps = hyper[8];
+  return h;
+}
+__device__ __forceinline__ void radam_elem(float& pi, float g, float& mi, float& vi, const RAdamHyper& h) {
+  const float gi = __fmul_rn(g, h.coef);
+  vi = __fmul_rn(vi, h.b2);
+  vi = __fadd_rn(vi, __fmul_rn(__fmul_rn(h.omb2, gi), gi));      // addcmul_(g, g, value=1-b2)
+  mi = __fadd_rn(__fmul_rn(mi, h.b1), __fmul_rn(h.omb1, gi));  // mul_(b1).add_(g, alpha=1-b1)
+  const float upd = h.rect ? __fdiv_rn(mi, __fadd_rn(__fsqrt_rn(vi), h.eps)) : mi;
+  pi = __fadd_rn(pi, __fmul_rn(h.val, upd));
+}
+
 __global__ __launch_bounds__(256) void radam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                     const float* __restrict__ hyper, const float* __restrict__ sumsq,
                                                     float max_norm) {
-  float coef = 1.f;
-  if (max_norm > 0.f && sumsq) {
-    const float tn = sqrtf(sumsq[0]);
-    coef = max_norm / (tn + 1e-6f);
-    coef = coef < 1.f ? coef : 1.f;
-  }
-  const float val = hyper[1];
-  const bool rect = hyper[2] != 0.f;
-  const float b1 = hyper[4], omb1 = hyper[5], b2 = hyper[6], omb2 = hyper[7], eps = hyper[8];
+  const RAdamHyper h = radam_hyper_load(hyper, sumsq, max_norm);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = __fmul_rn(g[i], coef);
-    float vi = __fmul_rn(v[i], b2);
-    vi = __fadd_rn(vi, __fmul_rn(__fmul_rn(omb2, gi), gi));      // addcmul_(g, g, value=1-b2)
-    float mi = __fadd_rn(__fmul_rn(m[i], b1), __fmul_rn(omb1, gi));  // mul_(b1).add_(g, alpha=1-b1)
-    const float upd = rect ? __fdiv_rn(mi, __fadd_rn(__fsqrt_rn(vi), eps)) : mi;
-    p[i] = __fadd_rn(p[i], __fmul_rn(val, upd));
+    float pi = p[i], mi = m[i], vi = v[i];
+    radam_elem(pi, g[i], mi, vi, h);
+    p[i] = pi;
     m[i] = mi;
     v[i] = vi;
   }
@@ -442,6 +459,135 @@ __global__ __launch_bounds__(256, 4) void adam_wn_kernel(float* __restrict__ p, 
   }
 }
 
+// Multi-tensor pair (vqx_multi_sq_norm, vqx_multi_adam_step): the gradients are
+// separate tensors whose addresses change every step, p / m / v stay flat.  A
+// launch takes up to kMultiMax tensors; their gradient pointers, flat offsets,
+// lengths and the block prefix of their 4096-element chunks travel by value in
+// the kernel arguments (no device table to upload, nothing to race with).
+constexpr int kMultiMax = 128, kMultiChunk = 4096;
+struct MultiArgs {
+  int n;
+  int blk[kMultiMax + 1];  // block prefix: tensor i owns blocks [blk[i], blk[i+1])
+  const float* g[kMultiMax];
+  int64_t off[kMultiMax];
+  int64_t numel[kMultiMax];
+};
+static_assert(sizeof(MultiArgs) + 64 <= 4096, "MultiArgs and the other arguments must fit the 4 KB kernel-argument segment");
+
+__device__ __forceinline__ int multi_find(const MultiArgs& A, int b) {
+  int lo = 0, hi = A.n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (A.blk[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// part[b] = sum g^2 over chunk b.  Thread t adds its 16 elements (4 groups of 4,
+// 1024 apart) in index order whether they are loaded 16 B at a time or singly,
+// so the partial does not depend on the gradient's alignment.
+__global__ __launch_bounds__(256) void multi_sq_kernel(MultiArgs A, float* __restrict__ part) {
+  __shared__ float red[16];
+  const int b = blockIdx.x;
+  const int t = multi_find(A, b);
+  const float* __restrict__ g = A.g[t];
+  float s = 0.f;
+  if (g) {  // (uniform across the block)
+    const int64_t len = A.numel[t];
+    const int64_t c0 = (int64_t)(b - A.blk[t]) * kMultiChunk;
+    const bool al = (((uintptr_t)g) & 15) == 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t j = c0 + (int64_t)threadIdx.x * 4 + 1024 * u;
+      if (al && j + 4 <= len) {
+        const f32x4_t x = *(const f32x4_t*)(g + j);
+        s = fmaf(x[0], x[0], s); s = fmaf(x[1], x[1], s); s = fmaf(x[2], x[2], s); s = fmaf(x[3], x[3], s);
+      } else {
+        for (int64_t e = j; e < len && e < j + 4; ++e) s = fmaf(g[e], g[e], s);
+      }
+    }
+  }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) part[b] = s;
+}
+
+__device__ __forceinline__ void radam1(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                       float* __restrict__ v, int64_t i, const RAdamHyper& h) {
+  float pi = p[i], mi = m[i], vi = v[i];
+  radam_elem(pi, g[i], mi, vi, h);
+  p[i] = pi;
+  m[i] = mi;
+  v[i] = vi;
+}
+__device__ __forceinline__ void radam4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                       float* __restrict__ v, int64_t i, const RAdamHyper& h) {
+  f32x4_t pv = *(const f32x4_t*)(p + i), gv = *(const f32x4_t*)(g + i);
+  f32x4_t mv = *(const f32x4_t*)(m + i), vv = *(const f32x4_t*)(v + i);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float pi = pv[e], mi = mv[e], vi = vv[e];
+    radam_elem(pi, gv[e], mi, vi, h);
+    pv[e] = pi;
+    mv[e] = mi;
+    vv[e] = vi;
+  }
+  *(f32x4_t*)(p + i) = pv;
+  *(f32x4_t*)(m + i) = mv;
+  *(f32x4_t*)(v + i) = vv;
+}
+
+// Tensor t updates p/m/v[off_t, off_t + numel_t) from its own gradient, a block
+// per 4096-element chunk: 16-B accesses when p + off, m + off, v + off and the
+// gradient are all 16-B aligned (decided per tensor, so uniform in a block),
+// one element at a time otherwise.  KIND 0: adam_elem (the bits of
+// adam_kernel); 1: radam_elem (the bits of radam_kernel).
+template <int KIND>
+__global__ __launch_bounds__(256) void multi_adam_kernel(float* __restrict__ p, float* __restrict__ m,
+                                                         float* __restrict__ v, const float* __restrict__ hyper,
+                                                         const float* __restrict__ sumsq, float max_norm,
+                                                         MultiArgs A) {
+  const int b = blockIdx.x;
+  const int t = multi_find(A, b);
+  const float* __restrict__ g = A.g[t];
+  const int64_t s0 = A.off[t], len = A.numel[t];
+  const int64_t c0 = (int64_t)(b - A.blk[t]) * kMultiChunk;
+  float* __restrict__ pp = p + s0;
+  float* __restrict__ mm = m + s0;
+  float* __restrict__ vv = v + s0;
+  const bool al = ((((uintptr_t)pp) | ((uintptr_t)mm) | ((uintptr_t)vv) | ((uintptr_t)g)) & 15) == 0;
+  if constexpr (KIND == 0) {
+    const AdamHyper h = adam_hyper_load(hyper, sumsq, max_norm);
+    if (al) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t j = c0 + (int64_t)threadIdx.x * 4 + 1024 * u;
+        if (j + 4 <= len) {
+          adam4(pp, g, mm, vv, j, h);
+        } else {
+          for (int64_t e = j; e < len && e < j + 4; ++e) adam1(pp, g, mm, vv, e, h);
+        }
+      }
+    } else {
+      for (int64_t j = c0 + threadIdx.x; j < len && j < c0 + kMultiChunk; j += 256) adam1(pp, g, mm, vv, j, h);
+    }
+  } else {
+    const RAdamHyper h = radam_hyper_load(hyper, sumsq, max_norm);
+    if (al) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t j = c0 + (int64_t)threadIdx.x * 4 + 1024 * u;
+        if (j + 4 <= len) {
+          radam4(pp, g, mm, vv, j, h);
+        } else {
+          for (int64_t e = j; e < len && e < j + 4; ++e) radam1(pp, g, mm, vv, e, h);
+        }
+      }
+    } else {
+      for (int64_t j = c0 + threadIdx.x; j < len && j < c0 + kMultiChunk; j += 256) radam1(pp, g, mm, vv, j, h);
+    }
+  }
+}
+
 }  // namespace vqx
 
 using namespace vqx;
@@ -584,4 +730,102 @@ extern "C" int vqx_radam_step(float* p, const float* g, float* m, float* v, int6
   hipLaunchKernelGGL(radam_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
                      hyper, sumsq, max_norm);
   return launch_status("vqx_radam_step");
+}
+
+extern "C" int vqx_multi_chunks(const int64_t* numel, int32_t n, int64_t* out) {
+  if (n < 0 || (n && !numel) || !out) { set_error("vqx_multi_chunks: bad arguments"); return -1; }
+  int64_t c = 0;
+  for (int i = 0; i < n; ++i) {
+    if (numel[i] < 0) { set_error("vqx_multi_chunks: tensor %d has a negative length", i); return -1; }
+    c += (numel[i] + kMultiChunk - 1) / kMultiChunk;
+  }
+  *out = c;
+  return 0;
+}
+
+extern "C" int vqx_multi_sq_norm(const float* const* grads, const int64_t* numel, int32_t n, float* partials,
+                                 int64_t n_partials, vqx_stream_t stream) {
+  if (n < 0 || (n && (!grads || !numel)) || n_partials < 0 || (n_partials && !partials)) {
+    set_error("vqx_multi_sq_norm: bad arguments");
+    return -1;
+  }
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (numel[i] < 0 || numel[i] > ((int64_t)1 << 40) || (((uintptr_t)grads[i]) & 3)) {
+      set_error("vqx_multi_sq_norm: tensor %d: bad length or a gradient that is not 4-B aligned", i);
+      return -1;
+    }
+    total += (numel[i] + kMultiChunk - 1) / kMultiChunk;
+  }
+  if (total != n_partials) {
+    set_error("vqx_multi_sq_norm: %lld chunks for %lld partials", (long long)total, (long long)n_partials);
+    return -1;
+  }
+  int64_t base = 0;
+  for (int i0 = 0; i0 < n; i0 += kMultiMax) {
+    MultiArgs A;
+    A.n = 0;
+    A.blk[0] = 0;
+    for (int i = i0; i < n && i < i0 + kMultiMax; ++i) {
+      const int64_t ch = (numel[i] + kMultiChunk - 1) / kMultiChunk;
+      if (ch == 0) continue;
+      if ((int64_t)A.blk[A.n] + ch > 0x7fffffff) { set_error("vqx_multi_sq_norm: too many chunks in one launch"); return -1; }
+      A.g[A.n] = grads[i];
+      A.off[A.n] = 0;
+      A.numel[A.n] = numel[i];
+      A.blk[A.n + 1] = A.blk[A.n] + (int)ch;
+      ++A.n;
+    }
+    if (A.n == 0) continue;
+    hipLaunchKernelGGL(multi_sq_kernel, dim3(A.blk[A.n]), dim3(256), 0, (hipStream_t)stream, A, partials + base);
+    base += A.blk[A.n];
+  }
+  return launch_status("vqx_multi_sq_norm");
+}
+
+extern "C" int vqx_multi_adam_step(float* p, float* m, float* v, int64_t n_flat, const int64_t* offset,
+                                   const int64_t* numel, const float* const* grads, int32_t n, const float* hyper,
+                                   const float* sumsq, float max_norm, int32_t kind, vqx_stream_t stream) {
+  if (!p || !m || !v || !hyper || n < 0 || n_flat < 0 || (n && (!offset || !numel || !grads)) ||
+      (kind != 0 && kind != 1)) {
+    set_error("vqx_multi_adam_step: bad arguments (kind 0 Adam, 1 RAdam)");
+    return -1;
+  }
+  if ((((uintptr_t)p) | ((uintptr_t)m) | ((uintptr_t)v)) & 3) {
+    set_error("vqx_multi_adam_step: p, m and v must be 4-B aligned");
+    return -1;
+  }
+  int64_t end = 0;
+  for (int i = 0; i < n; ++i) {  // ranges in order, inside [0, n_flat), not overlapping
+    if (numel[i] < 0 || offset[i] < end || numel[i] > n_flat || offset[i] > n_flat - numel[i] ||
+        (((uintptr_t)grads[i]) & 3)) {
+      set_error("vqx_multi_adam_step: tensor %d: range out of order or out of [0, %lld), or a gradient that is "
+                "not 4-B aligned", i, (long long)n_flat);
+      return -1;
+    }
+    end = offset[i] + numel[i];
+  }
+  for (int i0 = 0; i0 < n; i0 += kMultiMax) {
+    MultiArgs A;
+    A.n = 0;
+    A.blk[0] = 0;
+    for (int i = i0; i < n && i < i0 + kMultiMax; ++i) {
+      const int64_t ch = (numel[i] + kMultiChunk - 1) / kMultiChunk;
+      if (ch == 0 || !grads[i]) continue;  // no gradient: p, m and v stay as they are
+      if ((int64_t)A.blk[A.n] + ch > 0x7fffffff) { set_error("vqx_multi_adam_step: too many chunks in one launch"); return -1; }
+      A.g[A.n] = grads[i];
+      A.off[A.n] = offset[i];
+      A.numel[A.n] = numel[i];
+      A.blk[A.n + 1] = A.blk[A.n] + (int)ch;
+      ++A.n;
+    }
+    if (A.n == 0) continue;
+    if (kind == 0)
+      hipLaunchKernelGGL(multi_adam_kernel<0>, dim3(A.blk[A.n]), dim3(256), 0, (hipStream_t)stream, p, m, v, hyper,
+                         sumsq, max_norm, A);
+    else
+      hipLaunchKernelGGL(multi_adam_kernel<1>, dim3(A.blk[A.n]), dim3(256), 0, (hipStream_t)stream, p, m, v, hyper,
+                         sumsq, max_norm, A);
+  }
+  return launch_status("vqx_multi_adam_step");
 }

@@ -756,6 +756,21 @@ class Model(nn.Module):
         self.beta = arch.get("beta", 0.01)
         self.levels, self.use_gst, self.use_ema = levels, use_gst, use_ema
         self.compute_dtype = dtype
+        self._engine = None
+
+    def engine(self, device=None):
+        """The optimizer engine of this package's Trainer (engine/autograd_step.py:
+        flat parameters and moments, multi-tensor clip + Adam / RAdam), built
+        once per device and rebuilt when the parameters were moved."""
+        dev = device if device is not None else next(self.parameters()).device
+        dev = torch.device(dev)
+        if dev.type != "cuda":
+            raise RuntimeError("vqvae2.Model runs on the MI355X only (libvqx); move it with .cuda()")
+        e = self._engine
+        if e is None or e.device != dev or not e.params_intact():
+            from ..engine.autograd_step import AutogradEngine
+            e = self._engine = AutogradEngine(self, dev)
+        return e
 
     def forward(self, input):
         """(x (B, mel, T), y_idx (B, 1)) -> (xhat (B, mel, T), loss, loss dict)."""
@@ -815,3 +830,4 @@ class Model(nn.Module):
         for m in self.modules():
             if isinstance(m, (WNConv1d, ResampleConv1d)) and m.has_weight_norm:
                 m.remove_weight_norm()
+        self._engine = None  # the parameter list changed

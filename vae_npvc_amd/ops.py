@@ -859,6 +859,85 @@ def radam_step(p, g, m, v, hyper, sumsq, max_norm):
          stream_ptr())
 
 
+MULTI_MAX_TENSORS = 128  # include/vqx.h VQX_MULTI_MAX_TENSORS: tensors per launch of the multi-tensor kernels
+MULTI_CHUNK = 4096       # VQX_MULTI_CHUNK: elements per block and per partial
+
+
+def multi_layout(numels):
+    """(offsets, first partial, number of partials) of tensors packed densely in
+    list order: tensor i owns flat elements [offsets[i], offsets[i] + numels[i])
+    and the partials [first[i], first[i] + ceil(numels[i] / MULTI_CHUNK))."""
+    offsets, first, off, ch = [], [], 0, 0
+    for n in numels:
+        if n < 0:
+            raise ValueError("multi_layout: negative length")
+        offsets.append(off)
+        first.append(ch)
+        off += n
+        ch += -(-n // MULTI_CHUNK)
+    return offsets, first, ch
+
+
+class MultiTensorPlan:
+    """Host arrays of vqx_multi_sq_norm / vqx_multi_adam_step for a fixed list
+    of tensor lengths: numel and offset (dense in list order unless given) are
+    filled once, the gradient pointers by set_grads() before each use."""
+
+    def __init__(self, numels, offsets=None):
+        numels = [int(n) for n in numels]
+        dense, _, self.n_partials = multi_layout(numels)
+        offsets = dense if offsets is None else [int(o) for o in offsets]
+        if len(offsets) != len(numels):
+            raise ValueError("MultiTensorPlan: one offset per tensor")
+        self.n = len(numels)
+        self.numels, self.offsets = numels, offsets
+        self.numel_arr = (ctypes.c_int64 * max(self.n, 1))(*numels)
+        self.offset_arr = (ctypes.c_int64 * max(self.n, 1))(*offsets)
+        self.grad_arr = (ctypes.c_void_p * max(self.n, 1))()
+        chunks = ctypes.c_int64(0)
+        call("vqx_multi_chunks", ctypes.addressof(self.numel_arr), self.n, ctypes.byref(chunks))
+        if chunks.value != self.n_partials:
+            raise RuntimeError(f"multi_layout counts {self.n_partials} partials, the library {chunks.value}")
+
+    def set_grads(self, grads):
+        """grads: one contiguous float32 device tensor (or None) per tensor of
+        the plan; the caller keeps them alive until the launches have run."""
+        if len(grads) != self.n:
+            raise ValueError(f"MultiTensorPlan: {len(grads)} gradients for {self.n} tensors")
+        arr = self.grad_arr
+        for i, g in enumerate(grads):
+            if g is None:
+                arr[i] = None
+                continue
+            if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous() or g.numel() != self.numels[i]:
+                raise ValueError(f"MultiTensorPlan: gradient {i} must be a contiguous float32 device tensor of "
+                                 f"{self.numels[i]} elements")
+            arr[i] = g.data_ptr()
+
+
+def multi_sq_norm(plan, partials):
+    """partials[c] = sum g^2 over chunk c of the plan's gradients (zeros for a
+    missing gradient); partials has plan.n_partials floats."""
+    _check_cuda(partials)
+    if partials.numel() != plan.n_partials or partials.dtype != torch.float32 or not partials.is_contiguous():
+        raise ValueError(f"multi_sq_norm: partials must be {plan.n_partials} contiguous floats")
+    call("vqx_multi_sq_norm", ctypes.addressof(plan.grad_arr), ctypes.addressof(plan.numel_arr), plan.n,
+         ptr(partials), plan.n_partials, stream_ptr())
+    return partials
+
+
+def multi_adam_step(p, m, v, plan, hyper, sumsq, max_norm, kind=0):
+    """adam_step (kind 0) or radam_step (kind 1) of the flat p, m, v from the
+    plan's scattered gradients; a tensor without a gradient is left alone."""
+    _check_cuda(p, m, v, hyper)
+    if not (p.numel() == m.numel() == v.numel()) or any(t.dtype != torch.float32 or not t.is_contiguous()
+                                                        for t in (p, m, v)):
+        raise ValueError("multi_adam_step: p, m and v must be contiguous float32 tensors of one length")
+    call("vqx_multi_adam_step", ptr(p), ptr(m), ptr(v), p.numel(), ctypes.addressof(plan.offset_arr),
+         ctypes.addressof(plan.numel_arr), ctypes.addressof(plan.grad_arr), plan.n, ptr(hyper), ptr(sumsq),
+         max_norm, kind, stream_ptr())
+
+
 def convert_2d(src, dst, rows=None, cols=None):
     """dst[:rows, :cols] = src (dtype-converting, strided); src=None zero-fills."""
     rows = dst.shape[0] if rows is None else rows

@@ -9,6 +9,12 @@ with no host synchronisation; the optimizer state is saved in the
 torch.optim.Adam / reference RAdam state_dict format so reference checkpoints
 ({'model', 'optimizer', 'iteration'}) load both ways.
 
+`model_type: vae_npvc_amd.model.vqvae2` (the hierarchical model) has no fused
+forward: its forward and backward run under torch autograd and only the clip,
+Adam / RAdam and StepLR are fused (engine/autograd_step.py, the multi-tensor
+launches); train_step then returns the model's own loss dict.  Data parallel
+is not built for it and raises.
+
 Data parallel: when torch.distributed is initialised, each rank trains on its
 own shard (per-rank batch) and the engine all-reduces gradients and EMA
 statistics (vae_npvc_amd/parallel/ddp.py).
@@ -197,6 +203,9 @@ class Trainer(object):
         optimizer moments."""
         self.engine = self.model.engine(self.device)
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            if not self._fused_forward():  # never train unsynchronised
+                raise NotImplementedError(f"{type(self.model).__module__}: data parallel is not built for the "
+                                          f"hierarchical model (world size {dist.get_world_size()}); run one process")
             from ..parallel.ddp import Comm
             self.engine.attach_comm(Comm(overlap=self.grad_sync == "overlap"))
             dist.broadcast(self.engine.flat_p, 0)
@@ -210,6 +219,12 @@ class Trainer(object):
                                    sched_gamma=sp.get("gamma", 1.0) if self.scheduler_cfg else 1.0,
                                    kind=self.optim_kind)
 
+    def _fused_forward(self):
+        """True for the flat model's engine (forward and backward are its own
+        launches, train_step returns a workspace), False for the hierarchical
+        model's (engine/autograd_step.py: autograd, train_step returns the loss dict)."""
+        return getattr(self.engine, "fused_forward", True)
+
     def train_step(self, input, iteration=None):
         if not self.model.training:
             raise RuntimeError("train_step needs the model in training mode (valid_step restores it; "
@@ -217,6 +232,12 @@ class Trainer(object):
         x, y = input
         x = x.to(self.device, non_blocking=True).float().contiguous()
         y = y.to(self.device, non_blocking=True)
+        if not self._fused_forward():
+            # the hierarchical model (engine/autograd_step.py): forward and backward under
+            # autograd, the optimizer fused; the loss dict is the model's own (one readback)
+            detail = self.engine.train_step(x, y)
+            self.iteration += 1
+            return self.iteration, detail
         w = self.engine.train_step(x, y)
         # trainer/basic.py:74-77: the passed iteration is ignored and the
         # trainer's own counter advances (bin/train.py:126 feeds the returned
@@ -235,6 +256,9 @@ class Trainer(object):
         return loss_detail
 
     def valid_step(self, input):
+        if not self._fused_forward():
+            x, y = (t.to(self.device) for t in input)
+            return self.engine.valid_step(x, y)
         self.model.eval()
         with torch.no_grad():
             x, y = (t.to(self.device) for t in input)
