@@ -50,6 +50,14 @@ def relerr(a, b):
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
+def within_cap(y, ref, S, K):
+    """Per element |y - ref| <= (K + 16) 2^-23 S for an fp32 output of K products per element, S the
+    reference expression on absolute values (tests/conv_cases.py bounds): a condition on any
+    summation order, five orders below the norm-wise bf16 bar of TOL."""
+    err = (y.double().cpu() - ref.double().cpu()).abs()
+    return bool((err <= (K + 16) * 2.0 ** -23 * S.double().cpu()).all())
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("cin,cout,k,pro", [(80, 512, 3, None), (512, 512, 3, "lrelu"), (512, 128, 1, "lrelu"),
                                             (128, 80, 1, "relu"), (512, 640, 1, None), (512, 1024, 3, None)])
@@ -66,9 +74,15 @@ def test_conv_fwd(dtype, cin, cout, k, pro, tile):
     ops.conv_fwd(x, pack(w).to(dtype), y, T=T, cin=cin, cout=cout, ntaps=k, pad=(k - 1) // 2, prologue=proc,
                  bias=bias, out_f32=True)
     torch.cuda.synchronize()
-    ref = ref_conv(x.float().cpu(), pack(w).to(dtype).float().cpu().view(cout, k, cin).permute(0, 2, 1), B, T,
-                   (k - 1) // 2, pro) + bias.double().cpu()
+    w_op = pack(w).to(dtype).float().cpu().view(cout, k, cin).permute(0, 2, 1)
+    ref = ref_conv(x.float().cpu(), w_op, B, T, (k - 1) // 2, pro) + bias.double().cpu()
     assert relerr(y, ref) < TOL[dtype]
+    # per element, on the operand the kernel multiplies (the prologue's result rounded to `dtype`)
+    from conv_cases import apply_pro
+    x_op = apply_pro(x.cpu(), proc, 1.0).float()
+    ref_op = ref_conv(x_op, w_op, B, T, (k - 1) // 2) + bias.double().cpu()
+    S = ref_conv(x_op.abs(), w_op.abs(), B, T, (k - 1) // 2) + bias.double().cpu().abs()
+    assert within_cap(y, ref_op, S, k * cin)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -88,16 +102,24 @@ def test_conv_dgrad_wgrad(dtype, cin, cout, k, tile):
     yr.backward(dy.double().cpu().view(B, T, cout).permute(0, 2, 1))
     dx_ref = xr.grad.permute(0, 2, 1).reshape(B * T, cin)
     dw_ref = pack(wr.grad)
+    # the same gradients on absolute values: S of the per-element cap
+    xa = xr.detach().abs().requires_grad_(True)
+    wa = wr.detach().abs().requires_grad_(True)
+    F.conv1d(xa, wa, padding=pad).backward(dy.double().cpu().abs().view(B, T, cout).permute(0, 2, 1))
     if cin % 8 == 0:
         dx = torch.empty(B * T, cin, device=DEV, dtype=torch.float32)
         ops.conv_dgrad(dy, pack(w).to(dtype), dx, T=T, cin=cout, cout=cin, ntaps=k, pad=pad, out_f32=True)
         torch.cuda.synchronize()
         assert relerr(dx, dx_ref) < TOL[dtype]
+        assert within_cap(dx, dx_ref, xa.grad.permute(0, 2, 1).reshape(B * T, cin), k * cout)
     splits = 3
     slabs = torch.empty(splits, cout, k * cin, device=DEV)
     ops.conv_wgrad(dy, x, slabs, T=T, r_dim=cout, c_dim=cin, ntaps=k, pad=pad, splits=splits)
     torch.cuda.synchronize()
     assert relerr(slabs.sum(0), dw_ref) < TOL[dtype]
+    # a split sums at most 128 frames (256 frames in 3 splits of whole K-tiles); the splits are added
+    # in float64 here
+    assert within_cap(slabs.double().sum(0), dw_ref, pack(wa.grad), 128)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -132,6 +154,17 @@ def test_conv_dilated_and_wide_kernels(dtype, cin, cout, k, dil, T, tile):
     assert relerr(y, yr.detach().permute(0, 2, 1).reshape(B * T, cout)) < TOL[dtype]
     assert relerr(dx, xr.grad.permute(0, 2, 1).reshape(B * T, cin)) < TOL[dtype]
     assert relerr(slabs.sum(0), pack(wr.grad)) < TOL[dtype]
+    # per element, against the same expressions on absolute values
+    xa = xr.detach().abs().requires_grad_(True)
+    wa = wr.detach().abs().requires_grad_(True)
+    ya = F.conv1d(xa, wa, padding=pad, dilation=dil)
+    ya.backward(dy.double().cpu().abs().view(B, T, cout).permute(0, 2, 1))
+    assert within_cap(y, yr.detach().permute(0, 2, 1).reshape(B * T, cout),
+                      ya.detach().permute(0, 2, 1).reshape(B * T, cout), k * cin)
+    assert within_cap(dx, xr.grad.permute(0, 2, 1).reshape(B * T, cin),
+                      xa.grad.permute(0, 2, 1).reshape(B * T, cin), k * cout)
+    frames = -(-(-(-B * T // 3)) // 64) * 64   # most frames a split sums: whole K-tiles
+    assert within_cap(slabs.double().sum(0), pack(wr.grad), pack(wa.grad), frames)
     # the dilated ConvTranspose1d of the ResSkip blocks (conv_in, layers.py:199) as the
     # flipped-tap conv with pad (k-1)*dil - p, and its weight gradient (shift sign -1)
     xt = xr.detach().clone().requires_grad_(True)
