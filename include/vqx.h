@@ -840,6 +840,39 @@ int vqx_upsample_cat_bwd(const vqx_hier_level* levels, int32_t n_levels, int32_t
                          int32_t ldo, int32_t dout_dtype, vqx_stream_t stream);
 
 /*
+ * The frame-major input of the hierarchical model's first decoder straight
+ * from codes, in one launch (conversion: Model.synthesize; the reference's
+ * VectorQuantizer.decode, layers_vq.py:61-76, + Model.upsample + torch.cat).
+ * A level l is one of two kinds, told apart by `idx`:
+ *   dense   (idx NULL)  z_l [B][T_l][ld] f32 with C channels, exactly a level
+ *           of vqx_upsample_cat_fwd (the style vector, T_l = 1);
+ *   indexed (idx set)   idx_l [B][T_l] int64 into the codebook E [K][ld] f32
+ *           with C = D_l columns used:
+ *             out[b*T + t][off_l + c] = E[idx_l[b][src_l(t)]][c]
+ *           and with `normalize` != 0 that row divided by its own L2 norm
+ *           sqrt(sum_c E[k][c]^2), recomputed per output row (the reference's
+ *           target_norm * E / ||E|| with target_norm = 1).
+ * src_l(t) = min(t / (T / T_l), T_l - 1) and off_l = the running sum of C_l, as
+ * vqx_upsample_cat_fwd.  out [B*T][ldo] in VQX_F32 or VQX_BF16 (the f32 value
+ * rounded once to nearest even); columns from sum C_l up are not written.  The
+ * codebooks are only read; no atomics; equal arguments give equal bits.  The
+ * indices are trusted: the caller checks 0 <= idx < K.
+ * Up to 8 levels, passed by value to the kernel.  Limits (else -1): n_levels
+ * in 1..8; dtype F32 | BF16; B, T >= 1, B*T < 2^31; out, z, idx and E
+ * non-NULL where their kind reads them and 16-B aligned; C, ld, ldo multiples
+ * of 4, ld >= C; 1 <= T_l <= T; sum C_l <= ldo; K >= 1 for an indexed level.
+ * Additive: the ABI version does not change.
+ */
+typedef struct vqx_codes_level {
+  const void* z;         /* dense: [B][T_l][ld] f32; indexed: the codebook E [K][ld] f32 */
+  const int64_t* idx;    /* indexed: [B][T_l]; NULL makes the level dense               */
+  int32_t T_l, C, ld;    /* C = C_l (dense) or D_l (indexed)                            */
+  int32_t K, normalize;  /* indexed only                                                */
+} vqx_codes_level;
+int vqx_codes_upsample_cat(const vqx_codes_level* levels, int32_t n_levels, int32_t B, int32_t T, void* out,
+                           int32_t ldo, int32_t out_dtype, vqx_stream_t stream);
+
+/*
  * Masked layout change of the hierarchical encoder's backward (vqvae2.py:
  * 238-246, the encoder's second output `feat` = LeakyReLU_0.2(a)): the f32
  * (B, C, T) gradient into `feat`, through that LeakyReLU, frame-major:

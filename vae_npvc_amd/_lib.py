@@ -91,6 +91,11 @@ class HierLevel(ctypes.Structure):  # include/vqx.h vqx_hier_level
     _fields_ = [("z", c_void_p), ("T_l", c_int32), ("C", c_int32), ("ld", c_int32)]
 
 
+class CodesLevel(ctypes.Structure):  # include/vqx.h vqx_codes_level
+    _fields_ = [("z", c_void_p), ("idx", c_void_p), ("T_l", c_int32), ("C", c_int32), ("ld", c_int32),
+                ("K", c_int32), ("normalize", c_int32)]
+
+
 WN_COLREDUCE = 2
 WN_RESAMPLE, WN_RESAMPLE_T = 3, 4  # strided Conv1d / ConvTranspose1d (include/vqx.h)
 
@@ -206,6 +211,8 @@ _SIGS = {
                              c_void_p],
     "vqx_upsample_cat_bwd": [ctypes.POINTER(HierLevel), c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
                              c_void_p],
+    "vqx_codes_upsample_cat": [ctypes.POINTER(CodesLevel), c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                               c_void_p],
     "vqx_ntc_to_nct_scale": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p],
     "vqx_nct_to_ntc_lrelu_bwd": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float, c_void_p,
                                  c_int32, c_int32, c_void_p],

@@ -20,6 +20,11 @@
 // level) is below 32 frames, else 8; it depends on the shapes alone, so two
 // calls with the same shapes give the same bits.
 //
+// The first decoder's input from codes (include/vqx.h vqx_codes_upsample_cat):
+//   hier_codes_cat_kernel  one wavefront per output row; a level is dense (a
+//             level of the forward above) or an int64 index into a codebook,
+//             whose row is copied or divided by its own L2 norm.
+//
 // Masked layout change of the hierarchical encoder's backward (include/vqx.h
 // vqx_nct_to_ntc_lrelu_bwd): the (B, C, T) f32 gradient autograd hands to the
 // encoder's second output, through the LeakyReLU that produced it, as the
@@ -158,6 +163,69 @@ __global__ __launch_bounds__(HIER_BWD_LANES* HIER_BWD_PARTS) void hier_cat_bwd_k
   }
 }
 
+// Levels of vqx_codes_upsample_cat, by value.  src is the dense level or the
+// codebook; idx == nullptr marks a dense level.
+struct CodeLevels {
+  const float* src[HIER_MAX_LEVELS];
+  const int64_t* idx[HIER_MAX_LEVELS];
+  int T_l[HIER_MAX_LEVELS], rep[HIER_MAX_LEVELS], ld[HIER_MAX_LEVELS];
+  int gran[HIER_MAX_LEVELS];       // C_l / 4: 16-byte granules of the level in an output row
+  int off[HIER_MAX_LEVELS];        // first output column of the level
+  int normalize[HIER_MAX_LEVELS];
+  int n;
+};
+
+constexpr int CODES_WAVES = HIER_THREADS / 64;  // output rows per workgroup
+
+// One wavefront per output row; lane j moves granules j, j + 64, ... of each
+// level with 16-byte loads and stores (rows are 64 to 256 floats: one or two
+// rounds).  Everything that selects a path (row, level kind, normalize) is
+// wave-uniform, so the shuffles of wave_sum see all 64 lanes.  A normalised
+// level reads its codebook row twice: once for sum of squares (each lane adds
+// its granules' squares in column order, wave_sum adds the lanes), once to
+// write E[k][c] / sqrt(sum); the second read hits the cache.
+template <bool BF16>
+__global__ __launch_bounds__(HIER_THREADS) void hier_codes_cat_kernel(CodeLevels L, int64_t rows, int T,
+                                                                       void* __restrict__ out, int64_t ldo) {
+  const int lane = threadIdx.x & 63;
+  // the wave's index through readfirstlane: the compiler then keeps the row, the code index and the
+  // row addresses in scalar registers and branches on them without exec masks
+  const int64_t row = (int64_t)blockIdx.x * CODES_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int64_t b = row / T;
+  const int t = (int)(row - b * T);
+#pragma unroll
+  for (int l = 0; l < HIER_MAX_LEVELS; ++l) {
+    if (l >= L.n) break;
+    int s = t / L.rep[l];
+    s = s < L.T_l[l] ? s : L.T_l[l] - 1;
+    const int64_t frame = b * L.T_l[l] + s;
+    const int64_t src_row = L.idx[l] ? L.idx[l][frame] : frame;
+    const float* src = L.src[l] + src_row * L.ld[l];
+    const int G = L.gran[l];
+    const bool norm = L.idx[l] && L.normalize[l];
+    float len = 1.f;
+    if (norm) {
+      float ss = 0.f;
+      for (int g = lane; g < G; g += 64) {
+        const f32x4_t x = *(const f32x4_t*)(src + 4 * g);
+        ss += x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3];
+      }
+      len = sqrtf(wave_sum(ss));
+    }
+    const int64_t at = row * ldo + L.off[l];
+    for (int g = lane; g < G; g += 64) {
+      f32x4_t x = *(const f32x4_t*)(src + 4 * g);
+      if (norm) x = {x[0] / len, x[1] / len, x[2] / len, x[3] / len};
+      if constexpr (BF16) {
+        *(uint2*)((bf16_t*)out + at + 4 * g) = make_uint2(pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3]));
+      } else {
+        *(f32x4_t*)((float*)out + at + 4 * g) = x;
+      }
+    }
+  }
+}
+
 template <typename TA, typename TD>
 __global__ __launch_bounds__(256) void hier_lrelu_bwd_kernel(const float* __restrict__ g, int C, int T,
                                                              const TA* __restrict__ a, int64_t lda, float slope,
@@ -281,6 +349,43 @@ extern "C" int vqx_upsample_cat_bwd(const vqx_hier_level* levels, int32_t n_leve
   auto* fn = dout_dtype == VQX_BF16 ? hier_cat_bwd_kernel<true> : hier_cat_bwd_kernel<false>;
   hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(HIER_BWD_LANES, P), 0, s, L, items, T, dout, (int64_t)ldo);
   return launch_status("vqx_upsample_cat_bwd");
+}
+
+extern "C" int vqx_codes_upsample_cat(const vqx_codes_level* levels, int32_t n_levels, int32_t B, int32_t T, void* out,
+                                      int32_t ldo, int32_t out_dtype, vqx_stream_t stream) {
+  const char* who = "vqx_codes_upsample_cat";
+  if (!levels) { set_error("%s: null levels", who); return -1; }
+  if (n_levels < 1 || n_levels > HIER_MAX_LEVELS) { set_error("%s: n_levels = %d not in 1..%d", who, n_levels, HIER_MAX_LEVELS); return -1; }
+  if (out_dtype != VQX_F32 && out_dtype != VQX_BF16) { set_error("%s: bad dtype %d", who, out_dtype); return -1; }
+  if (B < 1 || T < 1 || (int64_t)B * T > INT32_MAX) { set_error("%s: B = %d, T = %d (B*T must fit 31 bits)", who, B, T); return -1; }
+  if (!out || !aligned16(out)) { set_error("%s: null or unaligned (16 B) out pointer", who); return -1; }
+  CodeLevels L = {};
+  L.n = n_levels;
+  int total = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    const vqx_codes_level& v = levels[l];
+    if (!v.z || !aligned16(v.z)) { set_error("%s: level %d: null or unaligned (16 B) %s pointer", who, l, v.idx ? "codebook" : "z"); return -1; }
+    if (v.idx && !aligned16(v.idx)) { set_error("%s: level %d: unaligned (16 B) idx pointer", who, l); return -1; }
+    if (v.T_l < 1 || v.T_l > T) { set_error("%s: level %d: T_l = %d not in 1..T = %d", who, l, v.T_l, T); return -1; }
+    if (v.C < 4 || v.C % 4 || v.ld % 4 || v.ld < v.C) { set_error("%s: level %d: C = %d / ld = %d must be multiples of 4, ld >= C", who, l, v.C, v.ld); return -1; }
+    if (v.idx && v.K < 1) { set_error("%s: level %d: K = %d codes", who, l, v.K); return -1; }
+    if ((int64_t)total + v.C > INT32_MAX) { set_error("%s: channel sum overflows", who); return -1; }
+    L.src[l] = (const float*)v.z;
+    L.idx[l] = v.idx;
+    L.T_l[l] = v.T_l;
+    L.rep[l] = T / v.T_l;
+    L.ld[l] = v.ld;
+    L.gran[l] = v.C / 4;
+    L.off[l] = total;
+    L.normalize[l] = v.idx && v.normalize;
+    total += v.C;
+  }
+  if (ldo % 4 || total > ldo) { set_error("%s: sum of C_l = %d exceeds ldo = %d (ldo a multiple of 4)", who, total, ldo); return -1; }
+  const int64_t rows = (int64_t)B * T;
+  const int64_t grid = (rows + CODES_WAVES - 1) / CODES_WAVES;
+  auto* fn = out_dtype == VQX_BF16 ? hier_codes_cat_kernel<true> : hier_codes_cat_kernel<false>;
+  hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(HIER_THREADS), 0, (hipStream_t)stream, L, rows, T, out, (int64_t)ldo);
+  return launch_status(who);
 }
 
 extern "C" int vqx_nct_to_ntc_lrelu_bwd(const float* g_nct, int32_t B, int32_t C, int32_t T, const void* a, int32_t lda,

@@ -79,6 +79,28 @@ class StyleTokenLayer(nn.Module):
             raise ValueError(f"StyleTokenLayer: z {tuple(z.shape)} is not (B, {self.ref_embed_dim}, T)")
         return self._apply_fn(z)
 
+    def pool_rows(self, z_rows, T):
+        """pool_forward without gradients on frame-major f32 rows z_rows [B*T, ref_embed_dim]
+        (no layout change): the style embedding [B, gst_token_dim]."""
+        if z_rows.dim() != 2 or z_rows.shape[1] != self.ref_embed_dim or z_rows.shape[0] % T:
+            raise ValueError(f"StyleTokenLayer: z_rows {tuple(z_rows.shape)} is not [B*{T}, {self.ref_embed_dim}]")
+        if not z_rows.is_cuda:
+            raise L.VqxError("StyleTokenLayer runs on the MI355X only (libvqx); move it and its input with .cuda()")
+        with torch.no_grad():
+            params = tuple(p.detach().float().contiguous() for p in self._params())
+            return _gst_rows(self.gst_heads, z_rows, T, params)[0]
+
+
+def _gst_rows(heads, z, T, params):
+    """vqx_gst_fwd on frame-major rows z [B*T, R] (T = 1: reference embeddings) with
+    the nine contiguous f32 parameters: (style [B, F], the workspace the backward reads)."""
+    B, R = z.shape[0] // T, z.shape[1]
+    (N, E), Fd = params[0].shape, params[1].shape[0]
+    ws = torch.empty(ops.gst_workspace(B, N, Fd, heads, R, E), device=z.device, dtype=F32)
+    style = torch.empty(B, Fd, device=z.device, dtype=F32)
+    ops.gst_fwd(z, T, params, heads, style, ws)
+    return style, ws
+
 
 class _GstFn(torch.autograd.Function):
     """x is (B, R) reference embeddings or (B, R, T) frames to pool."""
@@ -98,10 +120,7 @@ class _GstFn(torch.autograd.Function):
             if z.stride(1) != 1 or z.stride(0) < R:  # rows of a wider buffer are read in place
                 z = z.contiguous()
         params = tuple(p.detach().float().contiguous() for p in params)
-        (N, E), Fd = params[0].shape, params[1].shape[0]
-        ws = torch.empty(ops.gst_workspace(B, N, Fd, heads, R, E), device=dev, dtype=F32)
-        style = torch.empty(B, Fd, device=dev, dtype=F32)
-        ops.gst_fwd(z, T, params, heads, style, ws)
+        style, ws = _gst_rows(heads, z, T, params)
         if save:
             ctx.heads, ctx.T, ctx.xshape = heads, T, tuple(x.shape)
             ctx.save_for_backward(z, ws, *params)

@@ -218,6 +218,64 @@ class _Plan:
         return out
 
 
+def _decoder_rows(plan, x2, B, T, rows, T_levels, ts):
+    """The decoder's forward launches on frame-major operands: x2 [B*T, C] in
+    the compute dtype, the conditioning levels `rows` (f32 [B*T_l, C_l]) and the
+    flat tensor list `ts`.  Returns xhat f32 [B*T, final] and what the backward
+    reads (Tc, c_low, saved, wp, a_skip, f1, w1, w2)."""
+    dev, dt = x2.device, plan.dt
+    N = B * T
+    e = functools.partial(torch.empty, device=dev)
+    # conditioning at its own rate: c_low [B*Tc, cond] f32
+    if T_levels:
+        Tc = choose_tc(T, T_levels)
+        c_low = ops.upsample_cat_fwd(rows, B, Tc, e(B * Tc, plan.cond, dtype=F32))
+    else:
+        Tc, c_low = T, rows[0]
+    skip32 = e(N, plan.S, dtype=F32)
+    gn_part = e(B * 2 * 24, dtype=F32)
+    wp, saved, first = {}, [], True  # packed weights by tensor index; per step what the backward reads
+    cur = x2
+    for st in plan.steps:
+        if st[0] == "conv":
+            cv = st[1]
+            w = wp[cv.at] = _pack(ts[cv.at], cv.transposed, dt)
+            y = e(N, cv.cout, dtype=dt)
+            _fwd(cv, cur, w, y, T, bias=ts[cv.at + 1])
+            saved.append((cur,))
+            cur = y
+            continue
+        _, ci, cc, rs, ag = st
+        C = ci.cin
+        w_in, w_rs = _pack(ts[ci.at], True, dt), _pack(ts[rs.at], False, dt)
+        w_cc = _pack(ts[cc.at], False, F32)
+        wp[ci.at], wp[cc.at], wp[rs.at] = w_in, w_cc, w_rs
+        P = e(B * Tc, 2 * C, dtype=F32)  # conv_cond(c) + its bias, one row per conditioning frame
+        _fwd(cc, c_low, w_cc, P, Tc, bias=ts[cc.at + 1])
+        u, g, mr = e(N, 2 * C, dtype=dt), e(N, C, dtype=dt), e(B, 2, 2, dtype=F32)
+        seg = dict(rowbias=P, rowbias_T=Tc if Tc > 1 else 0)
+        if T % 128 == 0 and C % 128 == 0:  # GroupNorm statistics from the GEMM's epilogue tiles
+            gst = e((N // 128) * (2 * C // 128) * 4, dtype=F32)
+            _fwd(ci, cur, w_in, u, T, bias=ts[ci.at + 1], gn_stats=gst, gn_groups=2, **seg)
+            ops.gn_glu_fwd_tiles(u, g, T, gst, mr, ts[ag], ts[ag + 1])
+        else:
+            _fwd(ci, cur, w_in, u, T, bias=ts[ci.at + 1], **seg)
+            ops.groupnorm_stats(u, T, 2, gn_part, mr)
+            ops.gn_glu_fwd(u, g, T, mr, ts[ag], ts[ag + 1])
+        y = e(N, C, dtype=dt)
+        _fwd(rs, g, w_rs, y, T, bias=ts[rs.at + 1], res=cur, out2=skip32, split_col=C, out2_accumulate=not first)
+        first = False
+        saved.append((cur, u, g, mr))
+        cur = y
+    a_skip, f1 = e(N, plan.S, dtype=dt), e(N, plan.fin1.cout, dtype=dt)
+    xhat = e(N, plan.final, dtype=F32)
+    ops.scale_act_2d(skip32, a_skip, plan.scale, L.PRO_RELU)
+    w1, w2 = _pack(ts[plan.fin1.at], False, dt), _pack(ts[plan.fin2.at], False, dt)
+    _fwd(plan.fin1, a_skip, w1, f1, T, bias=ts[plan.fin1.at + 1], act=L.PRO_RELU)
+    _fwd(plan.fin2, f1, w2, xhat, T, bias=ts[plan.fin2.at + 1], out_f32=True)
+    return xhat, (Tc, c_low, saved, wp, a_skip, f1, w1, w2)
+
+
 class _DecoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, save, T_levels, x, *rest):
@@ -225,61 +283,12 @@ class _DecoderFn(torch.autograd.Function):
         cin, ts = rest[:nl], rest[nl:]
         if not x.is_cuda or not all(t.is_cuda for t in rest):
             raise L.VqxError("vqvae2.Decoder runs on the MI355X only (libvqx); move it and its inputs with .cuda()")
-        dev, dt = x.device, plan.dt
         B, _, T = x.shape
-        N = B * T
         ts = [t.detach().float() for t in ts]
-        e = functools.partial(torch.empty, device=dev)
-        # conditioning at its own rate: c_low [B*Tc, cond] f32
         rows = [_to_rows(z) for z in cin]
-        if T_levels:
-            Tc = choose_tc(T, T_levels)
-            c_low = ops.upsample_cat_fwd(rows, B, Tc, e(B * Tc, plan.cond, dtype=F32))
-        else:
-            Tc, c_low = T, rows[0]
-        x2 = e(N, x.shape[1], dtype=dt)
+        x2 = torch.empty(B * T, x.shape[1], device=x.device, dtype=plan.dt)
         ops.nct_to_ntc(x.float().contiguous(), x2)
-        skip32 = e(N, plan.S, dtype=F32)
-        gn_part = e(B * 2 * 24, dtype=F32)
-        wp, saved, first = {}, [], True  # packed weights by tensor index; per step what the backward reads
-        cur = x2
-        for st in plan.steps:
-            if st[0] == "conv":
-                cv = st[1]
-                w = wp[cv.at] = _pack(ts[cv.at], cv.transposed, dt)
-                y = e(N, cv.cout, dtype=dt)
-                _fwd(cv, cur, w, y, T, bias=ts[cv.at + 1])
-                saved.append((cur,))
-                cur = y
-                continue
-            _, ci, cc, rs, ag = st
-            C = ci.cin
-            w_in, w_rs = _pack(ts[ci.at], True, dt), _pack(ts[rs.at], False, dt)
-            w_cc = _pack(ts[cc.at], False, F32)
-            wp[ci.at], wp[cc.at], wp[rs.at] = w_in, w_cc, w_rs
-            P = e(B * Tc, 2 * C, dtype=F32)  # conv_cond(c) + its bias, one row per conditioning frame
-            _fwd(cc, c_low, w_cc, P, Tc, bias=ts[cc.at + 1])
-            u, g, mr = e(N, 2 * C, dtype=dt), e(N, C, dtype=dt), e(B, 2, 2, dtype=F32)
-            seg = dict(rowbias=P, rowbias_T=Tc if Tc > 1 else 0)
-            if T % 128 == 0 and C % 128 == 0:  # GroupNorm statistics from the GEMM's epilogue tiles
-                gst = e((N // 128) * (2 * C // 128) * 4, dtype=F32)
-                _fwd(ci, cur, w_in, u, T, bias=ts[ci.at + 1], gn_stats=gst, gn_groups=2, **seg)
-                ops.gn_glu_fwd_tiles(u, g, T, gst, mr, ts[ag], ts[ag + 1])
-            else:
-                _fwd(ci, cur, w_in, u, T, bias=ts[ci.at + 1], **seg)
-                ops.groupnorm_stats(u, T, 2, gn_part, mr)
-                ops.gn_glu_fwd(u, g, T, mr, ts[ag], ts[ag + 1])
-            y = e(N, C, dtype=dt)
-            _fwd(rs, g, w_rs, y, T, bias=ts[rs.at + 1], res=cur, out2=skip32, split_col=C, out2_accumulate=not first)
-            first = False
-            saved.append((cur, u, g, mr))
-            cur = y
-        a_skip, f1 = e(N, plan.S, dtype=dt), e(N, plan.fin1.cout, dtype=dt)
-        xhat = e(N, plan.final, dtype=F32)
-        ops.scale_act_2d(skip32, a_skip, plan.scale, L.PRO_RELU)
-        w1, w2 = _pack(ts[plan.fin1.at], False, dt), _pack(ts[plan.fin2.at], False, dt)
-        _fwd(plan.fin1, a_skip, w1, f1, T, bias=ts[plan.fin1.at + 1], act=L.PRO_RELU)
-        _fwd(plan.fin2, f1, w2, xhat, T, bias=ts[plan.fin2.at + 1], out_f32=True)
+        xhat, (Tc, c_low, saved, wp, a_skip, f1, w1, w2) = _decoder_rows(plan, x2, B, T, rows, T_levels, ts)
         if save:
             wp[plan.fin1.at], wp[plan.fin2.at] = w1, w2
             ctx.plan, ctx.dims, ctx.T_levels, ctx.Tc = plan, (B, T), T_levels, Tc
@@ -417,6 +426,29 @@ class Decoder(_Decoder):
         save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, *levels, *ts))
         return _DecoderFn.apply(self._plan, save, T_levels, x, *levels, *ts)
 
+    def forward_rows(self, x_rows, B, T, cond_rows):
+        """forward without gradients on frame-major operands: x_rows [B*T, C] in
+        the compute dtype (as vqx_codes_upsample_cat writes it) in place of
+        (B, C, T), so the first layout change is skipped; cond_rows the
+        conditioning levels as f32 [B*T_l, C_l] rows.  Returns xhat f32
+        [B*T, final] rows.  Nothing is kept for a backward."""
+        if self._plan is None:
+            self._plan = _Plan(self)
+        plan = self._plan
+        if not x_rows.is_cuda or x_rows.dim() != 2 or x_rows.dtype != plan.dt or x_rows.stride(1) != 1 \
+                or x_rows.shape[0] != B * T:
+            raise ValueError(f"vqvae2.Decoder: x_rows must be device [{B * T}, C] rows in {plan.dt}")
+        if any(r.dim() != 2 or r.dtype != F32 or r.shape[0] % B for r in cond_rows) \
+                or sum(r.shape[1] for r in cond_rows) != self.cond_ch:
+            raise ValueError(f"vqvae2.Decoder: the conditioning must be f32 [B*T_l, C_l] rows with sum C_l == "
+                             f"{self.cond_ch}")
+        T_levels = tuple(r.shape[0] // B for r in cond_rows)
+        for Tl in T_levels:
+            src_index(T, Tl)
+        with torch.no_grad():
+            ts = [t.detach().float() for t in _Plan.tensors(self)]
+            return _decoder_rows(plan, x_rows, B, T, list(cond_rows), T_levels, ts)[0]
+
 
 # ------------------------------------------------------------------ encoder
 class _EConv:
@@ -486,6 +518,102 @@ def _down_splits(cv, n, T, dt):
     return max(1, min(512 // max(1, tiles), n // 512))
 
 
+def _stage_frames(T_in, s):
+    """Output frames of a stage conv (kernel 2s, stride s, padding s//2 + s%2) on T_in frames."""
+    return T_in if s == 1 else (T_in + 2 * (s // 2 + s % 2) - 2 * s) // s + 1
+
+
+def _total_scale(enc):
+    """Total down-sampling of an Encoder: the product of its stage convs' strides."""
+    return math.prod(getattr(enc.encode[i], "scale", 1) for i in enc.stage_index)
+
+
+def _encoder_rows(plan, inp, B, T, ts, ragged=False):
+    """The encoder's forward launches on the frame-major input `inp` [B*T, C_in]
+    in the compute dtype.  Returns z f32 [B*T', z], feat [B*T', C] (the last
+    stage's LeakyReLU, compute dtype), T', and what the backward reads (saved, wp).
+
+    ragged (B == 1, nothing kept for a backward): a stage conv whose input length
+    J*s + r, 0 < r < s, is no multiple of its stride runs on the input zero-padded
+    to (J+1)*s rows, as J+1 folded frames, and its first floor((T_in + 2p - 2s)/s)
+    + 1 output rows are kept (J for an even s).  Every kept row reads real frames
+    or zeros where the strided conv reads its own padding, so this is exact; the
+    layers after it see the kept rows alone."""
+    dev, dt = inp.device, plan.dt
+    e = functools.partial(torch.empty, device=dev)
+    gn_part = e(B * 2 * 24, dtype=F32)
+    wp, saved, T_in = {}, [], T
+    for conv, blocks in plan.stages:
+        s, C = conv.scale, conv.cout
+        Ts = T_in // s
+        N = B * Ts
+        # every GEMM producing c_j also writes a_j = LeakyReLU(c_j), the operand of the
+        # next conv stack / stage conv / z_proj (vqvae2.py:224, layers.py:152)
+        if s == 1:
+            c, a = e(N, C, dtype=dt), e(N, C, dtype=dt)
+            w = wp[conv.at] = _pack(ts[conv.at], False, dt)
+            _fwd(conv, inp, w, c, T_in, bias=ts[conv.at + 1], act=L.PRO_LRELU, y2=a)
+        else:  # folded: s frames of cin channels as one frame of s*cin, 3 taps
+            w, norm = e(C, 3 * s * conv.cin, dtype=dt), e(C, dtype=F32)
+            ops.weight_norm_fwd(conv.mod._table(w, norm))
+            wp[conv.at] = (w, norm)
+            Tf = Ts  # folded frames the GEMM runs on
+            if T_in % s:
+                if not (ragged and B == 1):
+                    raise ValueError(f"vqvae2.Encoder: a stage of {T_in} frames is not a multiple of its stride {s}")
+                Tf, Ts = Ts + 1, _stage_frames(T_in, s)
+                if Ts < 1:
+                    raise ValueError(f"vqvae2.Encoder: T = {T} leaves a stage without a frame")
+                N = Ts
+                padded = e(Tf * s, conv.cin, dtype=dt)
+                ops.convert_2d(inp, padded, rows=T_in)
+                ops.zero_(padded[T_in:])
+                inp = padded
+            c, a = e(B * Tf, C, dtype=dt), e(B * Tf, C, dtype=dt)
+            ops.conv_fwd(inp.view(B * Tf, s * conv.cin), w, c, T=Tf, cin=s * conv.cin, cout=C, ntaps=3, pad=1,
+                         bias=ts[conv.at + 1], act=L.PRO_LRELU, y2=a)
+            c, a = c[:N], a[:N]
+        fuse = Ts % 128 == 0 and C % 128 == 0  # GroupNorm statistics from the GEMM's epilogue tiles
+        cs, acts, per_block = [c], [a], []
+        for convs, gn_at, skip in blocks:
+            src, hs, mrs, gs, gkw = acts[-1], [], [], [], {}
+            for l, (cv, ag) in enumerate(zip(convs, gn_at)):
+                last = l == len(convs) - 1
+                w = wp[cv.at] = _pack(ts[cv.at], False, dt)
+                h, mr = e(N, C, dtype=dt), e(B, 2, dtype=F32)
+                if fuse:
+                    gst = e((N // 128) * (C // 128) * 4, dtype=F32)
+                    _fwd(cv, src, w, h, Ts, bias=ts[cv.at + 1], gn_stats=gst, gn_groups=1)
+                    if last:
+                        gkw = dict(gn_tiles=gst)  # merged inside the skip GEMM
+                    else:
+                        ops.gn_finalize_tiles(gst, N, Ts, C, 1, mr)
+                else:
+                    _fwd(cv, src, w, h, Ts, bias=ts[cv.at + 1])
+                    ops.groupnorm_stats(h, Ts, 1, gn_part, mr)
+                if not last:  # LeakyReLU(GN(h)): the next conv's operand (layers.py:156-161)
+                    g = e(N, C, dtype=dt)
+                    ops.gn_lrelu_fwd(h, g, Ts, mr, ts[ag], ts[ag + 1])
+                    gs.append(g)
+                    src = g
+                hs.append(h)
+                mrs.append(mr)
+            w = wp[skip.at] = _pack(ts[skip.at], False, dt)
+            c, a = e(N, C, dtype=dt), e(N, C, dtype=dt)
+            _fwd(skip, cs[-1], w, c, Ts, bias=ts[skip.at + 1], gn_h=hs[-1], gn_mr=mrs[-1], gn_gamma=ts[gn_at[-1]],
+                 gn_beta=ts[gn_at[-1] + 1], act=L.PRO_LRELU, y2=a, **gkw)
+            cs.append(c)
+            acts.append(a)
+            per_block.append((hs, mrs, gs))
+        saved.append((inp, T_in, Ts, cs, acts, per_block))
+        inp, T_in = acts[-1], Ts
+    zp = plan.z_proj
+    w = wp[zp.at] = _pack(ts[zp.at], False, dt)
+    z = e(B * T_in, zp.cout, dtype=F32)
+    _fwd(zp, inp, w, z, T_in, bias=ts[zp.at + 1], out_f32=True)
+    return z, inp, T_in, saved, wp
+
+
 class _EncoderFn(torch.autograd.Function):
     """engine/step.py encoder_fwd / encoder_bwd composed from ops.*, with the
     second output `feat` = the last stage's LeakyReLU and a gradient into it."""
@@ -494,72 +622,15 @@ class _EncoderFn(torch.autograd.Function):
     def forward(ctx, plan, save, x, *ts):
         if not x.is_cuda or not all(t.is_cuda for t in ts if t is not None):
             raise L.VqxError("vqvae2.Encoder runs on the MI355X only (libvqx); move it and its input with .cuda()")
-        dev, dt = x.device, plan.dt
         B, _, T = x.shape
         ts = [None if t is None else t.detach().float() for t in ts]
-        e = functools.partial(torch.empty, device=dev)
-        inp = ops.nct_to_ntc(x.float().contiguous(), e(B * T, x.shape[1], dtype=dt))
-        gn_part = e(B * 2 * 24, dtype=F32)
-        wp, saved, T_in = {}, [], T
-        for conv, blocks in plan.stages:
-            s, C = conv.scale, conv.cout
-            Ts = T_in // s
-            N = B * Ts
-            # every GEMM producing c_j also writes a_j = LeakyReLU(c_j), the operand of the
-            # next conv stack / stage conv / z_proj (vqvae2.py:224, layers.py:152)
-            c, a = e(N, C, dtype=dt), e(N, C, dtype=dt)
-            if s == 1:
-                w = wp[conv.at] = _pack(ts[conv.at], False, dt)
-                _fwd(conv, inp, w, c, T_in, bias=ts[conv.at + 1], act=L.PRO_LRELU, y2=a)
-            else:  # folded: s frames of cin channels as one frame of s*cin, 3 taps
-                w, norm = e(C, 3 * s * conv.cin, dtype=dt), e(C, dtype=F32)
-                ops.weight_norm_fwd(conv.mod._table(w, norm))
-                wp[conv.at] = (w, norm)
-                ops.conv_fwd(inp.view(N, s * conv.cin), w, c, T=Ts, cin=s * conv.cin, cout=C, ntaps=3, pad=1,
-                             bias=ts[conv.at + 1], act=L.PRO_LRELU, y2=a)
-            fuse = Ts % 128 == 0 and C % 128 == 0  # GroupNorm statistics from the GEMM's epilogue tiles
-            cs, acts, per_block = [c], [a], []
-            for convs, gn_at, skip in blocks:
-                src, hs, mrs, gs, gkw = acts[-1], [], [], [], {}
-                for l, (cv, ag) in enumerate(zip(convs, gn_at)):
-                    last = l == len(convs) - 1
-                    w = wp[cv.at] = _pack(ts[cv.at], False, dt)
-                    h, mr = e(N, C, dtype=dt), e(B, 2, dtype=F32)
-                    if fuse:
-                        gst = e((N // 128) * (C // 128) * 4, dtype=F32)
-                        _fwd(cv, src, w, h, Ts, bias=ts[cv.at + 1], gn_stats=gst, gn_groups=1)
-                        if last:
-                            gkw = dict(gn_tiles=gst)  # merged inside the skip GEMM
-                        else:
-                            ops.gn_finalize_tiles(gst, N, Ts, C, 1, mr)
-                    else:
-                        _fwd(cv, src, w, h, Ts, bias=ts[cv.at + 1])
-                        ops.groupnorm_stats(h, Ts, 1, gn_part, mr)
-                    if not last:  # LeakyReLU(GN(h)): the next conv's operand (layers.py:156-161)
-                        g = e(N, C, dtype=dt)
-                        ops.gn_lrelu_fwd(h, g, Ts, mr, ts[ag], ts[ag + 1])
-                        gs.append(g)
-                        src = g
-                    hs.append(h)
-                    mrs.append(mr)
-                w = wp[skip.at] = _pack(ts[skip.at], False, dt)
-                c, a = e(N, C, dtype=dt), e(N, C, dtype=dt)
-                _fwd(skip, cs[-1], w, c, Ts, bias=ts[skip.at + 1], gn_h=hs[-1], gn_mr=mrs[-1], gn_gamma=ts[gn_at[-1]],
-                     gn_beta=ts[gn_at[-1] + 1], act=L.PRO_LRELU, y2=a, **gkw)
-                cs.append(c)
-                acts.append(a)
-                per_block.append((hs, mrs, gs))
-            saved.append((inp, T_in, Ts, cs, acts, per_block))
-            inp, T_in = acts[-1], Ts
-        zp = plan.z_proj
-        w = wp[zp.at] = _pack(ts[zp.at], False, dt)
-        z = e(B * T_in, zp.cout, dtype=F32)
-        _fwd(zp, inp, w, z, T_in, bias=ts[zp.at + 1], out_f32=True)
+        inp = ops.nct_to_ntc(x.float().contiguous(), torch.empty(B * T, x.shape[1], device=x.device, dtype=plan.dt))
+        z, feat, T_out, saved, wp = _encoder_rows(plan, inp, B, T, ts)
         ctx.set_materialize_grads(False)
         if save:
             ctx.plan, ctx.B = plan, B
             ctx.keep = (saved, wp, ts)
-        return _to_nct(z, B, T_in), _to_nct(inp, B, T_in)
+        return _to_nct(z, B, T_out), _to_nct(feat, B, T_out)
 
     @staticmethod
     @once_differentiable
@@ -684,6 +755,31 @@ class Encoder(_Encoder):
         save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, *ts) if t is not None)
         return _EncoderFn.apply(plan, save, x, *ts)
 
+    def forward_rows(self, x_rows, B, T):
+        """forward without gradients on the frame-major input x_rows [B*T, C_in]
+        in the compute dtype: (z f32 [B*T', z_channels] rows, feat [B*T', C]
+        rows in the compute dtype, T').  One utterance (B == 1) may have any
+        length that leaves every stage a frame (_encoder_rows states the
+        ragged stages); forward itself keeps refusing such a T."""
+        if self._plan is None:
+            self._plan = _EncPlan(self)
+        plan = self._plan
+        if not x_rows.is_cuda or x_rows.dim() != 2 or x_rows.dtype != plan.dt or x_rows.stride(1) != 1 \
+                or tuple(x_rows.shape) != (B * T, self.in_ch):
+            raise ValueError(f"vqvae2.Encoder: x_rows must be device [{B * T}, {self.in_ch}] rows in {plan.dt}")
+        ragged, T_in = False, T
+        for conv, _ in plan.stages:
+            ragged |= T_in % conv.scale != 0
+            T_in = _stage_frames(T_in, conv.scale)
+            if T_in < 1:
+                raise ValueError(f"vqvae2.Encoder: T = {T} leaves a stage without a frame")
+        if ragged and B != 1:
+            raise ValueError(f"vqvae2.Encoder: T = {T} is not a multiple of every stage's stride; such lengths are "
+                             f"converted one utterance at a time (B == 1), got B = {B}")
+        with torch.no_grad():
+            ts = [None if t is None else t.detach().float() for t in _EncPlan.tensors(self, plan)]
+            return _encoder_rows(plan, x_rows, B, T, ts, ragged=ragged)[:3]
+
 
 # ------------------------------------------------------------------ model
 class _LogLossFn(torch.autograd.Function):
@@ -724,6 +820,11 @@ class Model(nn.Module):
     is built for conditioning: each decoder receives its low-rate levels as a
     list; only the input of decoders[0] goes through upsample_cat.  The loss
     dict comes from one readback of the packed scalars at the end.
+
+    Conversion: analyze(x) -> the codes forward picks, synthesize((codes, y))
+    -> xhat from codes, convert((x, y)) = the two together = the xhat of
+    forward((x, y)).  All three run without gradients and write no parameter
+    or buffer; one utterance at a time may have any length.
 
     Not built (NotImplementedError): use_ema: true (EMAVectorQuantizer.forward
     inside the hierarchy), jitter_p != 0, and encode / decode / infer, whose
@@ -812,6 +913,136 @@ class Model(nn.Module):
             losses[f"entropy.{k}"] = host[3 + 2 * k]
             losses[f"quanti_err.{k}"] = host[4 + 2 * k]
         return xhat, loss, losses
+
+    # ------------------------------------------------------------ conversion
+    # The reference defines conversion through forward: xhat of forward((x, y')) is x
+    # rendered with speaker y'.  y enters decoders[0] alone, so the codes of every
+    # level depend on x only: analyze gives them, synthesize renders them.
+    def _is_style(self, i):
+        return self.use_gst and i == self.levels - 1
+
+    def analyze(self, x):
+        """x (B, mel, T) -> the codes forward would pick, one entry per level in
+        level order: int64 indices (B, T_i) of a quantized level, the style
+        embedding (B, F, 1) f32 of a style-token top level.  Computed in
+        forward's order (top first, decoders[2] and decoders[1] producing the
+        lower levels' quantizer inputs) on frame-major rows throughout, under
+        no_grad; no parameter or buffer is written (forward renormalises the
+        codebooks in place; here they are normalised on the fly).  One utterance
+        (B == 1) may have any length that leaves every level a frame."""
+        if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != self.encoders[0].in_ch:
+            raise ValueError(f"vqvae2.Model.analyze: x must be (B, {self.encoders[0].in_ch}, T)")
+        if not x.is_cuda:
+            raise L.VqxError("vqvae2.Model runs on the MI355X only (libvqx); move it and its inputs with .cuda()")
+        with torch.no_grad():
+            B, _, T = x.shape
+            dt = _DT[self.compute_dtype]
+            e = functools.partial(torch.empty, device=x.device)
+            feat, Ti, zs = ops.nct_to_ntc(x.float().contiguous(), e(B * T, x.shape[1], dtype=dt)), T, []
+            for enc in self.encoders:
+                z, feat, Ti = enc.forward_rows(feat, B, Ti)
+                zs.append((z, Ti))
+            codes, cond = [None] * self.levels, []  # cond: the quantized levels as f32 rows, top first
+            z, Ti = zs.pop()
+            for i in reversed(range(self.levels)):
+                q = self.quantizers[i]
+                if self._is_style(i):
+                    style = q.pool_rows(z, Ti)
+                    codes[i] = style.unsqueeze(-1)
+                    cond.append(style)
+                else:
+                    idx = codes[i] = q.encode(z.view(B, Ti, -1), time_last=False)
+                    if i > 0:
+                        cond.append(ops.codes_upsample_cat([(idx, q.embeddings.detach(), q.normalize)], B, Ti,
+                                                           e(B * Ti, q.z_dim, dtype=F32)))
+                if i > 0:
+                    z, Ti = zs.pop()
+                    xin = z if dt == F32 else ops.convert_2d(z, e(z.shape, dtype=dt))
+                    z = self.decoders[i].forward_rows(xin, B, Ti, cond)
+            return codes
+
+    def _check_codes(self, codes, y_idx, time):
+        """synthesize's validation, on the host before any libvqx launch (one
+        readback: the extremes of every index tensor, from torch's aminmax).
+        Returns (codes as a list, B, T)."""
+        who = "vqvae2.Model.synthesize"
+        codes = list(codes)
+        if len(codes) != self.levels or not all(torch.is_tensor(c) for c in codes):
+            raise ValueError(f"{who}: codes must hold one tensor per level ({self.levels})")
+        B, width, spans = codes[0].shape[0], 0, []
+        for i, c in enumerate(codes):
+            q = self.quantizers[i]
+            if self._is_style(i):
+                if c.dim() != 3 or not c.is_floating_point() or c.shape[1] % 4:
+                    raise ValueError(f"{who}: level {i} is a style level: a float (B, F, T_i) tensor, F a multiple of 4")
+                width += c.shape[1]
+            else:
+                if c.dim() != 2 or c.dtype != torch.int64:
+                    raise ValueError(f"{who}: level {i} is a quantized level: int64 indices (B, T_i)")
+                width += q.z_dim
+                if c.numel():
+                    spans += list(torch.aminmax(c))
+            if c.shape[0] != B:
+                raise ValueError(f"{who}: level {i} has batch size {c.shape[0]}, level 0 has {B}")
+        if not torch.is_tensor(y_idx) or y_idx.dim() != 2 or y_idx.shape[0] != B:
+            raise ValueError(f"{who}: y_idx must be (B, 1) speaker indices with B = {B}")
+        if codes[0].dim() != 2 and time is None:
+            raise ValueError(f"{who}: give `time` when level 0 is not an index tensor")
+        T = int(time) if time is not None else codes[0].shape[1] * _total_scale(self.encoders[0])
+        for i, c in enumerate(codes):
+            try:
+                src_index(T, c.shape[-1])
+            except ValueError:
+                raise ValueError(f"{who}: level {i} has {c.shape[-1]} frames, which do not stretch to T = {T} "
+                                 "(1 <= T_i <= T)") from None
+        want = self.decoders[0].layers[0].cin
+        if width != want:
+            raise ValueError(f"{who}: the levels' channels sum to {width}, decoders[0] takes {want}")
+        if spans:
+            ext = torch.stack(spans).tolist()  # the one readback
+            quantized = [i for i in range(self.levels) if not self._is_style(i) and codes[i].numel()]
+            for k, i in enumerate(quantized):
+                K = self.quantizers[i].z_num
+                if ext[2 * k] < 0 or ext[2 * k + 1] >= K:
+                    raise ValueError(f"{who}: level {i} has indices in {ext[2 * k]}..{ext[2 * k + 1]}, the codebook "
+                                     f"holds 0..{K - 1}")
+        return codes, B, T
+
+    def synthesize(self, input, time=None):
+        """((codes, y_idx (B, 1)), time) -> xhat (B, mel, T): decoders[0] on the
+        codes of `analyze` (entries may come from different calls, e.g. the style
+        of another utterance) with the speaker embedding as conditioning, as
+        forward.  One vqx_codes_upsample_cat launch builds the decoder's
+        frame-major input from the indices, channels stacked top level first.
+        T = `time`, else codes[0]'s frames times encoder 0's down-sampling.
+        Under no_grad; writes no parameter or buffer.  Bad codes raise
+        ValueError before any libvqx launch."""
+        codes, y_idx = input
+        codes, B, T = self._check_codes(codes, y_idx, time)
+        if not all(c.is_cuda for c in codes) or not y_idx.is_cuda:
+            raise L.VqxError("vqvae2.Model runs on the MI355X only (libvqx); move it and its inputs with .cuda()")
+        with torch.no_grad():
+            levels = []
+            for i in reversed(range(self.levels)):
+                c, q = codes[i], self.quantizers[i]
+                if self._is_style(i):
+                    levels.append(c.float().reshape(B, -1) if c.shape[2] == 1 else _to_rows(c))
+                else:
+                    c = c.contiguous()
+                    if c.data_ptr() % 16:  # a slice of a longer index tensor: the kernel reads aligned pointers
+                        c = c.clone()
+                    levels.append((c, q.embeddings.detach(), q.normalize))
+            dec = self.decoders[0]
+            rows = torch.empty(B * T, dec.layers[0].cin, device=y_idx.device, dtype=_DT[self.compute_dtype])
+            ops.codes_upsample_cat(levels, B, T, rows)
+            y = self.embeds(y_idx[..., :1]).reshape(B, -1)
+            return _to_nct(dec.forward_rows(rows, B, T, [y]), B, T)
+
+    def convert(self, input):
+        """(x (B, mel, T), y_idx (B, 1)) -> x rendered with speaker y_idx:
+        synthesize((analyze(x), y_idx), time=T), the xhat of forward((x, y_idx))."""
+        x, y_idx = input
+        return self.synthesize((self.analyze(x), y_idx), time=x.shape[2])
 
     def encode(self, input):
         raise NotImplementedError("vqvae2.Model.encode: the reference's version reads self.encoder and self.quantizer, "

@@ -1116,6 +1116,45 @@ def upsample_cat_bwd(dlevels, B, T, dout):
     return dlevels
 
 
+def codes_upsample_cat(levels, B, T, out):
+    """The first decoder's frame-major input from codes in one launch
+    (vqx_codes_upsample_cat).  A level is a dense f32 tensor [B*T_l, C_l] (as in
+    upsample_cat_fwd) or a tuple (idx int64 (B, T_l), codebook f32 [K, D],
+    normalize): out[b*T + t, off_l + c] = codebook[idx[b, src_l(t)], c], divided
+    by the row's L2 norm with `normalize`.  out f32 or bf16 [B*T, >= sum C_l].
+    The indices are not checked here (the caller's job, Model.synthesize)."""
+    if not 1 <= len(levels) <= HIER_MAX_LEVELS:
+        raise ValueError(f"codes_upsample_cat: {len(levels)} levels, 1..{HIER_MAX_LEVELS} are supported")
+    arr, total = (L.CodesLevel * len(levels))(), 0
+    for e, lv in zip(arr, levels):
+        if torch.is_tensor(lv):
+            z = lv
+            _check_cuda(z)
+            if z.dtype != torch.float32 or z.dim() != 2 or z.stride(1) != 1 or z.shape[0] % B:
+                raise ValueError("codes_upsample_cat: a dense level must be f32 [B*T_l, C_l] rows with unit column "
+                                 "stride")
+            e.z, e.idx, e.T_l, e.C, e.ld = ptr(z), None, z.shape[0] // B, z.shape[1], z.stride(0)
+            _rows(z, z.shape[0], e.ld, e.C, "codes_upsample_cat level")
+        else:
+            idx, E, normalize = lv
+            _check_cuda(idx, E)
+            if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != B or not idx.is_contiguous():
+                raise ValueError(f"codes_upsample_cat: indices must be a contiguous int64 ({B}, T_l) tensor")
+            if E.dtype != torch.float32 or E.dim() != 2 or E.stride(1) != 1:
+                raise ValueError("codes_upsample_cat: a codebook must be f32 [K, D] rows with unit column stride")
+            e.z, e.idx, e.T_l, e.C, e.ld = ptr(E), ptr(idx), idx.shape[1], E.shape[1], E.stride(0)
+            e.K, e.normalize = E.shape[0], int(bool(normalize))
+            _span(idx, idx.numel(), "codes_upsample_cat idx")
+            _rows(E, e.K, e.ld, e.C, "codes_upsample_cat codebook")
+        total += e.C
+    _check_cuda(out)
+    if out.dim() != 2 or out.shape[0] != B * T or out.stride(1) != 1:
+        raise ValueError(f"codes_upsample_cat: out must be [{B * T}, C] rows with unit column stride")
+    _rows(out, out.shape[0], out.stride(0), total, "codes_upsample_cat out")
+    call("vqx_codes_upsample_cat", arr, len(levels), B, T, ptr(out), out.stride(0), dt_code(out.dtype), stream_ptr())
+    return out
+
+
 def nct_to_ntc_lrelu_bwd(g_nct, a, slope, dst):
     """dst[b*T + t, c] = g_nct[b, c, t] * (a[b*T + t, c] > 0 ? 1 : slope)
     (vqx_nct_to_ntc_lrelu_bwd): the f32 (B, C, T) gradient into a LeakyReLU's
