@@ -510,6 +510,28 @@ int vqx_vq_commit_bwd_cs(const float* z, const float* zq, int64_t n_rows, int32_
 int vqx_time_gather(const void* x, void* y, int32_t B, int32_t T, int32_t C, const int32_t* src_t,
                     int32_t dtype, vqx_stream_t stream);
 
+/* One training batch cut from a device-resident corpus (additive, ABI 130
+ * unchanged): what dataset/utt2mel_spk.py's items and torch's default
+ * collation give, without the per-item file reads and the batch copy.
+ * corpus is device f32 [n_rows][mel], frame-major, the utterances back to
+ * back; spk_table is device int64 [n_utts].  For item b < B:
+ *   x[b][c][t] = corpus[row0[b] + t][c]   for t <  len[b]
+ *   x[b][c][t] = 0                        for len[b] <= t < T
+ *   y[b]       = spk_table[utt[b]]
+ * x is f32 (B, mel, T) contiguous and y int64 [B]; every element of both is
+ * written (no zero-fill by the caller).  row0 (int64), len and utt (int32)
+ * are HOST arrays of B entries, read during the call and passed to the
+ * kernel by value, 192 items a launch (as vqx_gather_rows_host passes its
+ * rows): no host-to-device copy on the stream, no allocation, no
+ * synchronisation.  Every item is validated before the first launch --
+ * 0 <= len[b] <= T, row0[b] >= 0, row0[b] + len[b] <= n_rows,
+ * 0 <= utt[b] < n_utts, and B, T, mel >= 1 (T, mel <= 2^20) -- and a failure
+ * names the item in vqx_last_error() and launches nothing, so the kernel
+ * reads no row outside the corpus. */
+int vqx_crop_batch(const float* corpus, int64_t n_rows, int32_t mel, const int64_t* spk_table, int32_t n_utts,
+                   const int64_t* row0, const int32_t* len, const int32_t* utt, int32_t B, int32_t T, float* x,
+                   int64_t* y, vqx_stream_t stream);
+
 /* Speaker embedding lookup (layers.py:42-54, nn.Embedding) and its
  * backward scatter-add (dense weight gradient). */
 int vqx_embedding_fwd(const float* weight, const int64_t* ids, int32_t B, int32_t D, float* out,

@@ -154,6 +154,8 @@ _SIGS = {
     "vqx_vq_commit_bwd": [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int32, c_void_p],
     "vqx_vq_commit_bwd_cs": [c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_int32, c_void_p, c_void_p],
     "vqx_time_gather": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p],
+    "vqx_crop_batch": [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                       c_void_p, c_void_p, c_void_p],
     "vqx_embedding_fwd": [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
     "vqx_embedding_bwd": [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
     "vqx_embedding_bwd_rows": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p],

@@ -24,9 +24,13 @@ needs:
   each checkpoint.
 
 At world size 1 the loop is the reference's: a shuffled DataLoader drawing
-from the global torch generator.  One deliberate fix: when no validation ever
-ran, the reference copies the nonexistent `iter.0` and crashes
-(bin/train.py:173); here the copy is skipped with a log line.
+from the global torch generator.  A `dataset_type` module that defines
+`loader(dataset, batch_size, shuffle, drop_last, sampler, generator)`
+(dataset/resident.py: batches cut on the device) supplies the training and
+validation loaders instead of DataLoader, from the same values.  One
+deliberate fix: when no validation ever ran, the reference copies the
+nonexistent `iter.0` and crashes (bin/train.py:173); here the copy is skipped
+with a log line.
 
     python -m vae_npvc_amd.bin.train -c conf.yaml --output_dir exp --train_dir data/train [--valid_dir ...]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m vae_npvc_amd.bin.train ...
@@ -155,18 +159,28 @@ def train(args):
         if config["global_batch_size"] % world:
             raise ValueError(f"global_batch_size {config['global_batch_size']} is not a multiple of {world} ranks")
         batch_size = config["global_batch_size"] // world
+    # a dataset module that defines `loader` (dataset/resident.py) builds its own
+    # batches from the same values; num_jobs and pin_memory do not apply to it
+    make_loader = getattr(dataset_module, "loader", None)
     train_set = Dataset(train_dir, config)
     if ddp:
         sampler = ShardSampler(train_set, world, rank, shuffle=True, seed=seed, drop_last=True)
         # crop offsets come from the workers' Python RNG, seeded from this
         # generator: per-rank streams, and the global generator is not consumed
-        train_loader = DataLoader(train_set, num_workers=num_jobs, sampler=sampler, batch_size=batch_size,
-                                  pin_memory=True, drop_last=True, collate_fn=collate_fn,
-                                  generator=torch.Generator().manual_seed(seed + 1000003 * (rank + 1)))
+        generator = torch.Generator().manual_seed(seed + 1000003 * (rank + 1))
+        if make_loader is not None:
+            train_loader = make_loader(train_set, batch_size=batch_size, shuffle=False, drop_last=True,
+                                       sampler=sampler, generator=generator)
+        else:
+            train_loader = DataLoader(train_set, num_workers=num_jobs, sampler=sampler, batch_size=batch_size,
+                                      pin_memory=True, drop_last=True, collate_fn=collate_fn, generator=generator)
     else:
         sampler = None
-        train_loader = DataLoader(train_set, num_workers=num_jobs, shuffle=True, batch_size=batch_size,
-                                  pin_memory=True, drop_last=True, collate_fn=collate_fn)
+        if make_loader is not None:
+            train_loader = make_loader(train_set, batch_size=batch_size, shuffle=True, drop_last=True)
+        else:
+            train_loader = DataLoader(train_set, num_workers=num_jobs, shuffle=True, batch_size=batch_size,
+                                      pin_memory=True, drop_last=True, collate_fn=collate_fn)
     if len(train_loader) == 0:
         raise ValueError(f"{len(train_set)} utterances give no full batch of {batch_size} per rank on {world} rank(s)")
 
@@ -175,8 +189,11 @@ def train(args):
         try:
             vbs = config.get("valid_batch_size", config.get("batch_size", 1))
             valid_set = Dataset(valid_dir, config, valid=True)
-            valid_loader = DataLoader(valid_set, num_workers=num_jobs, shuffle=False, batch_size=vbs,
-                                      pin_memory=True, drop_last=False, collate_fn=collate_fn)
+            if make_loader is not None:
+                valid_loader = make_loader(valid_set, batch_size=vbs, shuffle=False, drop_last=False)
+            else:
+                valid_loader = DataLoader(valid_set, num_workers=num_jobs, shuffle=False, batch_size=vbs,
+                                          pin_memory=True, drop_last=False, collate_fn=collate_fn)
         except Exception as e:  # the reference's bare except disables validation silently
             logging.getLogger("logger").warning("validation disabled: %r", e)
             valid_set, valid_loader = [], None
@@ -192,6 +209,9 @@ def train(args):
     logger.info("Output directory: {}".format(output_dir))
     logger.info("Training utterances: {}".format(len(train_set)))
     logger.info("Validation utterances: {}".format(len(valid_set)))
+    for s in (train_set, valid_set):  # a dataset that loaded at construction (before this logger existed) says what
+        if getattr(s, "load_info", None):
+            logger.info(s.load_info)
     if ddp:
         logger.info("Data parallel: {} ranks ({}), {} utterances per rank per epoch, batch {} per rank".format(
             world, backend, len(sampler), batch_size))

@@ -763,6 +763,32 @@ def gather_rows_host(src, rows, out):
     return out
 
 
+def crop_batch(corpus, spk_table, row0, length, utt, x, y):
+    """x[b, :, :length[b]] = corpus[row0[b]:row0[b] + length[b]].T, zeros up to
+    T; y[b] = spk_table[utt[b]] (vqx_crop_batch).  corpus [n_rows, mel] f32 and
+    spk_table [n_utts] int64 are device tensors; row0 (int64), length and utt
+    (int32) are host tensors of B entries, passed to the kernel by value (no
+    copy on the stream); x (B, mel, T) f32 and y (B,) or (B, 1) int64 are
+    written whole.  The library validates every item before it launches."""
+    _check_cuda(corpus, spk_table, x, y)
+    B = x.shape[0] if x.dim() == 3 else -1
+    if (corpus.dim() != 2 or corpus.dtype != torch.float32 or not corpus.is_contiguous() or B < 0
+            or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[1] != corpus.shape[1]):
+        raise ValueError("crop_batch: corpus [n_rows, mel] and x (B, mel, T) must be contiguous f32 with one mel")
+    if spk_table.dtype != torch.int64 or spk_table.dim() != 1 or not spk_table.is_contiguous():
+        raise ValueError("crop_batch: spk_table must be a contiguous int64 vector")
+    if y.dtype != torch.int64 or y.numel() != B or not y.is_contiguous():
+        raise ValueError("crop_batch: y must be contiguous int64 with B elements")
+    for t, dt, what in ((row0, torch.int64, "row0"), (length, torch.int32, "length"), (utt, torch.int32, "utt")):
+        if t.device.type != "cpu" or t.dtype != dt or t.numel() != B or not t.is_contiguous():
+            raise ValueError(f"crop_batch: {what} must be a contiguous host {dt} tensor of B = {B} entries")
+    _span(corpus, corpus.numel(), "crop_batch corpus")
+    _span(x, x.numel(), "crop_batch x")
+    call("vqx_crop_batch", ptr(corpus), corpus.shape[0], corpus.shape[1], ptr(spk_table), spk_table.numel(),
+         row0.data_ptr(), length.data_ptr(), utt.data_ptr(), B, x.shape[2], ptr(x), ptr(y), stream_ptr())
+    return x, y
+
+
 def vq_commit_bwd(z, zq, scale, dz):
     call("vqx_vq_commit_bwd", ptr(z), ptr(zq), z.numel(), scale, ptr(dz), dt_code(dz.dtype), stream_ptr())
     return dz
