@@ -917,6 +917,34 @@ int vqx_nct_to_ntc_lrelu_bwd(const float* g_nct, int32_t B, int32_t C, int32_t T
 int vqx_ntc_to_nct_scale(const float* y, int32_t ldy, int32_t B, int32_t C, int32_t T, const float* g,
                          float* x_nct, vqx_stream_t stream);
 
+/*
+ * Layout changes of a quantizer level under autograd with the jitter
+ * (layers_vq.py:353-379) folded in, and the EMA level's commitment gradient.
+ * src_t is a device int32 [T] neighbour map (frame t shows frame src_t[t]);
+ * NULL is the identity.  All three validate on the host before launching
+ * (null required pointer, T < 1, C < 1, B < 1 or B > 65535, B*T*C >= 2^31 ->
+ * -1 with vqx_last_error), are stream-ordered without host synchronisation
+ * and go through the 32 x 32 LDS tile of vqx_nct_to_ntc / vqx_ntc_to_nct.
+ * Additive: the ABI version does not change.
+ *
+ * vqx_ntc_to_nct_gather: x_nct[b][c][t] = y[b*T + src_t[t]][c], f32 (B, C, T)
+ *   from rows in dtype (VQX_F32 | VQX_BF16), ldy >= C.  A map entry outside
+ *   0..T-1 is clamped into it.
+ * vqx_nct_to_ntc_keep: y[b*T + t][c] = src_t[t] == t ? g_nct[b][c][t] : 0,
+ *   rounded once to dtype: the jitter's backward (a replaced frame is a
+ *   detached copy and passes no gradient; a source frame keeps only its own).
+ * vqx_vq_commit_bwd_g: dz = (s * g[0]) * (z - zq) from frame-major f32 z, zq
+ *   [B*T][D]; dz is f32 (B, D, T) when nct != 0, else [B*T][D] rows.  g is a
+ *   device scalar (NULL: 1).  The product s*g[0] is formed in fp32 first, then
+ *   one subtraction and one multiplication per element.
+ */
+int vqx_ntc_to_nct_gather(const void* y, int32_t ldy, int32_t dtype, int32_t B, int32_t C, int32_t T,
+                          const int32_t* src_t, float* x_nct, vqx_stream_t stream);
+int vqx_nct_to_ntc_keep(const float* g_nct, int32_t B, int32_t C, int32_t T, const int32_t* src_t, void* y,
+                        int32_t ldy, int32_t dtype, vqx_stream_t stream);
+int vqx_vq_commit_bwd_g(const float* z, const float* zq, int32_t B, int32_t D, int32_t T, float s, const float* g,
+                        int32_t nct, float* dz, vqx_stream_t stream);
+
 /* ABI 130: vqx_conv_args.rowbias_T appended (segmented row bias of the forward
  * epilogue; 0 or 1 keeps every earlier call's bits) and vqx_upsample_cat_*. */
 /* ABI version (major*100 + minor); VQX_ABI_VERSION is what this header describes. */

@@ -218,6 +218,10 @@ _SIGS = {
     "vqx_ntc_to_nct_scale": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p],
     "vqx_nct_to_ntc_lrelu_bwd": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float, c_void_p,
                                  c_int32, c_int32, c_void_p],
+    "vqx_ntc_to_nct_gather": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p],
+    "vqx_nct_to_ntc_keep": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p],
+    "vqx_vq_commit_bwd_g": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_int32, c_void_p,
+                            c_void_p],
 }
 EXPORTS = tuple(_SIGS) + ("vqx_last_error", "vqx_version")
 

@@ -29,6 +29,58 @@ __global__ void ntc_to_nct_kernel(const T* __restrict__ y, int ldy, int B, int C
   }
 }
 
+// ntc_to_nct_kernel with the jitter gather folded in: frame t of the output is
+// row src[t] of the input (src NULL: row t).  A map entry is clamped into
+// 0..T-1, so no map can send a read outside y.
+template <typename T>
+__global__ __launch_bounds__(256) void ntc_to_nct_gather_kernel(const T* __restrict__ y, int64_t ldy, int C, int T_,
+                                                                const int* __restrict__ src, float* __restrict__ x) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z;
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    float v = 0.f;
+    if (c < C && t < T_) {
+      int s = src ? src[t] : t;
+      s = s < 0 ? 0 : (s >= T_ ? T_ - 1 : s);
+      v = Elem<T>::ld(y, ((int64_t)b * T_ + s) * ldy + c);
+    }
+    tile[i][tx] = v;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    if (c < C && t < T_) x[((int64_t)b * C + c) * T_ + t] = tile[tx][i];
+  }
+}
+
+// nct_to_ntc_tile with the jitter's backward folded in: a frame whose map
+// entry is not itself was overwritten by a detached copy and passes no
+// gradient (src NULL: every frame kept).
+template <typename T>
+__global__ __launch_bounds__(256) void nct_to_ntc_keep_kernel(const float* __restrict__ g, int C, int T_,
+                                                              const int* __restrict__ src, T* __restrict__ y,
+                                                              int64_t ldy) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z;
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    tile[i][tx] = (c < C && t < T_) ? g[((int64_t)b * C + c) * T_ + t] : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    if (c < C && t < T_) {
+      const bool keep = !src || src[t] == t;
+      Elem<T>::st(y, ((int64_t)b * T_ + t) * ldy + c, keep ? tile[tx][i] : 0.f);
+    }
+  }
+}
+
 template <typename T>
 __global__ void time_gather_kernel(const T* __restrict__ x, T* __restrict__ y, int B, int T_, int C,
                                    const int* __restrict__ src) {
@@ -140,6 +192,45 @@ extern "C" int vqx_ntc_to_nct(const void* y, int32_t ldy, int32_t dtype, int32_t
   else
     hipLaunchKernelGGL(ntc_to_nct_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)y, ldy, B, C, T, x);
   return launch_status("vqx_ntc_to_nct");
+}
+
+// host checks shared by the two jitter layout changes; 0 when the launch may go
+static int jitter_layout_check(const char* who, const void* a, const void* b, int32_t B, int32_t C, int32_t T,
+                               int32_t ldy, int32_t dtype) {
+  if (!a || !b) { set_error("%s: null pointer", who); return -1; }
+  if (dtype != VQX_F32 && dtype != VQX_BF16) { set_error("%s: bad dtype %d", who, dtype); return -1; }
+  if (T < 1 || C < 1 || B < 1 || B > 65535 || ldy < C) {
+    set_error("%s: B = %d, C = %d, T = %d, ldy = %d (1 <= B <= 65535, C, T >= 1, ldy >= C)", who, B, C, T, ldy);
+    return -1;
+  }
+  if ((int64_t)B * T * C >= (1LL << 31)) { set_error("%s: B*T*C must be < 2^31", who); return -1; }
+  return 0;
+}
+
+extern "C" int vqx_ntc_to_nct_gather(const void* y, int32_t ldy, int32_t dtype, int32_t B, int32_t C, int32_t T,
+                                     const int32_t* src_t, float* x_nct, vqx_stream_t stream) {
+  const char* who = "vqx_ntc_to_nct_gather";
+  if (jitter_layout_check(who, y, x_nct, B, C, T, ldy, dtype)) return -1;
+  const dim3 grid((unsigned)((T + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)B);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == VQX_BF16)
+    hipLaunchKernelGGL(ntc_to_nct_gather_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)y, (int64_t)ldy, C, T, src_t, x_nct);
+  else
+    hipLaunchKernelGGL(ntc_to_nct_gather_kernel<float>, grid, dim3(256), 0, s, (const float*)y, (int64_t)ldy, C, T, src_t, x_nct);
+  return launch_status(who);
+}
+
+extern "C" int vqx_nct_to_ntc_keep(const float* g_nct, int32_t B, int32_t C, int32_t T, const int32_t* src_t, void* y,
+                                   int32_t ldy, int32_t dtype, vqx_stream_t stream) {
+  const char* who = "vqx_nct_to_ntc_keep";
+  if (jitter_layout_check(who, g_nct, y, B, C, T, ldy, dtype)) return -1;
+  const dim3 grid((unsigned)((T + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)B);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == VQX_BF16)
+    hipLaunchKernelGGL(nct_to_ntc_keep_kernel<bf16_t>, grid, dim3(256), 0, s, g_nct, C, T, src_t, (bf16_t*)y, (int64_t)ldy);
+  else
+    hipLaunchKernelGGL(nct_to_ntc_keep_kernel<float>, grid, dim3(256), 0, s, g_nct, C, T, src_t, (float*)y, (int64_t)ldy);
+  return launch_status(who);
 }
 
 extern "C" int vqx_time_gather(const void* x, void* y, int32_t B, int32_t T, int32_t C, const int32_t* src_t,

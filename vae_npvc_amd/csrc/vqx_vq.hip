@@ -670,6 +670,40 @@ __global__ void commit_bwd_kernel(const float* __restrict__ z, const float* __re
     Elem<T>::st(dz, i, scale * __fsub_rn(z[i], zq[i]));
 }
 
+// commit_bwd with the scale's second factor read on the device (g NULL: 1):
+// the product s*g[0] first, then one subtraction and one multiplication an
+// element.  NCT: dz is written as (B, D, T) through the 32 x 32 LDS tile of
+// ntc_to_nct_kernel (grid: T tiles, D tiles, B); else as rows (grid-stride).
+template <bool NCT>
+__global__ __launch_bounds__(256) void commit_bwd_g_kernel(const float* __restrict__ z, const float* __restrict__ zq,
+                                                           int D, int T_, int64_t n, float scale,
+                                                           const float* __restrict__ g, float* __restrict__ dz) {
+  const float s = g ? __fmul_rn(scale, g[0]) : scale;
+  if constexpr (NCT) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.z;
+    const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int i = ty; i < 32; i += 8) {
+      const int t = t0 + i, c = c0 + tx;
+      float v = 0.f;
+      if (c < D && t < T_) {
+        const int64_t e = ((int64_t)b * T_ + t) * D + c;
+        v = __fmul_rn(__fsub_rn(z[e], zq[e]), s);
+      }
+      tile[i][tx] = v;
+    }
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8) {
+      const int c = c0 + i, t = t0 + tx;
+      if (c < D && t < T_) dz[((int64_t)b * D + c) * T_ + t] = tile[tx][i];
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+      dz[i] = __fmul_rn(__fsub_rn(z[i], zq[i]), s);
+  }
+}
+
 // commit_bwd with the column sums of the stored dz: block p = row part p,
 // thread = (4-column chunk, row group); rows of a group four at a time (their
 // loads in flight together), the groups' sums added in order through LDS.
@@ -920,6 +954,27 @@ extern "C" int vqx_vq_commit_bwd(const float* z, const float* zq, int64_t count,
     hipLaunchKernelGGL(commit_bwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, zq, count, scale,
                        (float*)dz);
   return launch_status("vqx_vq_commit_bwd");
+}
+
+extern "C" int vqx_vq_commit_bwd_g(const float* z, const float* zq, int32_t B, int32_t D, int32_t T, float s,
+                                   const float* g, int32_t nct, float* dz, vqx_stream_t stream) {
+  const char* who = "vqx_vq_commit_bwd_g";
+  if (!z || !zq || !dz) { set_error("%s: null pointer", who); return -1; }
+  if (T < 1 || D < 1 || B < 1 || B > 65535) {
+    set_error("%s: B = %d, D = %d, T = %d (1 <= B <= 65535, D, T >= 1)", who, B, D, T);
+    return -1;
+  }
+  const int64_t n = (int64_t)B * T * D;
+  if (n >= (1LL << 31)) { set_error("%s: B*T*D must be < 2^31", who); return -1; }
+  hipStream_t st = (hipStream_t)stream;
+  if (nct) {
+    const dim3 grid((unsigned)((T + 31) / 32), (unsigned)((D + 31) / 32), (unsigned)B);
+    hipLaunchKernelGGL(commit_bwd_g_kernel<true>, grid, dim3(256), 0, st, z, zq, D, T, n, s, g, dz);
+  } else {
+    const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(commit_bwd_g_kernel<false>, dim3(grid), dim3(256), 0, st, z, zq, D, T, n, s, g, dz);
+  }
+  return launch_status(who);
 }
 
 // ===================================================================

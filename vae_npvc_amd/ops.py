@@ -1211,6 +1211,58 @@ def ntc_to_nct_scale(y, g, x_nct):
     return x_nct
 
 
+def _src_map(src_t, T, what):
+    if src_t is not None and (not src_t.is_cuda or src_t.dtype != torch.int32 or src_t.numel() != T
+                              or not src_t.is_contiguous()):
+        raise ValueError(f"{what}: src_t must be a contiguous device int32 tensor of T = {T} entries")
+
+
+def ntc_to_nct_gather(y, src_t, x_nct):
+    """x_nct[b, c, t] = y[b*T + src_t[t], c] (vqx_ntc_to_nct_gather): f32 / bf16 rows
+    to f32 (B, C, T) with the jitter's neighbour map (device int32 [T]; None:
+    the plain transposition) folded in."""
+    _check_cuda(y, x_nct)
+    B, C, T = x_nct.shape
+    if x_nct.dtype != torch.float32 or not x_nct.is_contiguous() or y.dim() != 2 or y.shape[0] != B * T \
+            or y.shape[1] < C or y.stride(1) != 1:
+        raise ValueError(f"ntc_to_nct_gather: y [{B * T}, >= {C}] rows, contiguous f32 x")
+    _src_map(src_t, T, "ntc_to_nct_gather")
+    _rows(y, B * T, y.stride(0), C, "ntc_to_nct_gather y")
+    call("vqx_ntc_to_nct_gather", ptr(y), y.stride(0), dt_code(y.dtype), B, C, T, ptr(src_t), ptr(x_nct), stream_ptr())
+    return x_nct
+
+
+def nct_to_ntc_keep(g_nct, src_t, y):
+    """y[b*T + t, c] = g_nct[b, c, t] where src_t[t] == t, else 0 (vqx_nct_to_ntc_keep):
+    the jitter's backward folded into the layout change; y f32 / bf16 rows."""
+    _check_cuda(g_nct, y)
+    B, C, T = g_nct.shape
+    if g_nct.dtype != torch.float32 or not g_nct.is_contiguous() or y.dim() != 2 or y.shape[0] != B * T \
+            or y.shape[1] < C or y.stride(1) != 1:
+        raise ValueError(f"nct_to_ntc_keep: contiguous f32 g (B, C, T), y [{B * T}, >= {C}] rows")
+    _src_map(src_t, T, "nct_to_ntc_keep")
+    _rows(y, B * T, y.stride(0), C, "nct_to_ntc_keep y")
+    call("vqx_nct_to_ntc_keep", ptr(g_nct), B, C, T, ptr(src_t), ptr(y), y.stride(0), dt_code(y.dtype), stream_ptr())
+    return y
+
+
+def vq_commit_bwd_g(z, zq, B, T, s, g, dz):
+    """dz = (s * g[0]) * (z - zq) (vqx_vq_commit_bwd_g) from contiguous f32 rows
+    z, zq [B*T, D]; dz f32 (B, D, T) or [B*T, D] rows (told by its shape); g a
+    one-element f32 device tensor or None (= 1): no readback."""
+    _check_cuda(z, zq, dz, g)
+    D = z.shape[1]
+    nct = dz.dim() == 3
+    if tuple(z.shape) != (B * T, D) or zq.shape != z.shape or tuple(dz.shape) != ((B, D, T) if nct else (B * T, D)) \
+            or not (z.is_contiguous() and zq.is_contiguous() and dz.is_contiguous()) \
+            or any(t.dtype != torch.float32 for t in (z, zq, dz)):
+        raise ValueError("vq_commit_bwd_g: contiguous f32 z, zq [B*T, D]; dz (B, D, T) or [B*T, D]")
+    if g is not None and (g.dtype != torch.float32 or g.numel() != 1):
+        raise ValueError("vq_commit_bwd_g: the upstream gradient must be a one-element f32 device tensor")
+    call("vqx_vq_commit_bwd_g", ptr(z), ptr(zq), B, D, T, float(s), ptr(g), int(nct), ptr(dz), stream_ptr())
+    return dz
+
+
 def cu_masked_stream(reserve_cus):
     """A torch ExternalStream on all but `reserve_cus` CUs of the current
     device (vqx_stream_create_cu_mask) and the CU count it may use; release it
