@@ -860,6 +860,19 @@ int vqx_upsample_cat_fwd(const vqx_hier_level* levels, int32_t n_levels, int32_t
                          int32_t ldo, int32_t out_dtype, vqx_stream_t stream);
 int vqx_upsample_cat_bwd(const vqx_hier_level* levels, int32_t n_levels, int32_t B, int32_t T, const void* dout,
                          int32_t ldo, int32_t dout_dtype, vqx_stream_t stream);
+/*
+ * vqx_upsample_cat_bwd with the levels' storage type chosen: the same kernel,
+ * the same fp32 sums in the same fixed order (no atomics; equal shapes give
+ * equal bits), each level stored as level_dtype: VQX_F32 (bit-equal to
+ * vqx_upsample_cat_bwd) or VQX_BF16, z_l then bf16 [B][T_l][ld] and every sum
+ * rounded once to nearest even.  It hands a level decoder its output gradient
+ * in the compute dtype without a convert launch (model/vqvae2b.py).
+ * Limits (else -1): those of vqx_upsample_cat_bwd (ld_l counts elements of
+ * level_dtype), and level_dtype F32 | BF16.  Additive: the ABI version does
+ * not change.
+ */
+int vqx_upsample_cat_bwd_to(const vqx_hier_level* levels, int32_t n_levels, int32_t B, int32_t T, const void* dout,
+                            int32_t ldo, int32_t dout_dtype, int32_t level_dtype, vqx_stream_t stream);
 
 /*
  * The frame-major input of the hierarchical model's first decoder straight

@@ -213,6 +213,8 @@ _SIGS = {
                              c_void_p],
     "vqx_upsample_cat_bwd": [ctypes.POINTER(HierLevel), c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
                              c_void_p],
+    "vqx_upsample_cat_bwd_to": [ctypes.POINTER(HierLevel), c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                                c_int32, c_void_p],
     "vqx_codes_upsample_cat": [ctypes.POINTER(CodesLevel), c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
                                c_void_p],
     "vqx_ntc_to_nct_scale": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p],

@@ -18,7 +18,9 @@
 // added in ascending chunk order starting from 0.f.  P = 1 when the longest
 // segment of the call (the tail segment T - (T_l - 1) * (T / T_l) of some
 // level) is below 32 frames, else 8; it depends on the shapes alone, so two
-// calls with the same shapes give the same bits.
+// calls with the same shapes give the same bits.  vqx_upsample_cat_bwd_to runs
+// the same kernel with the final store templated: the fp32 sum as it is, or
+// rounded once to bf16 (nearest even) into a bf16 level of the same ld.
 //
 // The first decoder's input from codes (include/vqx.h vqx_codes_upsample_cat):
 //   hier_codes_cat_kernel  one wavefront per output row; a level is dense (a
@@ -112,8 +114,19 @@ __global__ __launch_bounds__(HIER_THREADS) void hier_cat_fwd_kernel(HierLevels L
   }
 }
 
+// The backward's one store of an item's four sums: fp32, or bf16 rounded once
+// (the level is then bf16 [B][T_l][ld]; at is the element offset in either type).
+template <bool OUT_BF16>
+__device__ __forceinline__ void hier_store_sum(float* z, int64_t at, const f32x4_t& v) {
+  if constexpr (OUT_BF16) {
+    *(uint2*)((bf16_t*)z + at) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+  } else {
+    *(f32x4_t*)(z + at) = v;
+  }
+}
+
 // blockDim = (HIER_BWD_LANES, P): lane x owns one item, chunk y of its segment.
-template <bool BF16>
+template <bool BF16, bool OUT_BF16>
 __global__ __launch_bounds__(HIER_BWD_LANES* HIER_BWD_PARTS) void hier_cat_bwd_kernel(HierLevels L, int64_t items, int T,
                                                                                       const void* __restrict__ dout,
                                                                                       int64_t ldo) {
@@ -151,7 +164,7 @@ __global__ __launch_bounds__(HIER_BWD_LANES* HIER_BWD_PARTS) void hier_cat_bwd_k
     dst = (b * p.T_l + s) * p.ld + 4 * g;
   }
   if (P == 1) {
-    if (live) *(f32x4_t*)(p.z + dst) = acc;
+    if (live) hier_store_sum<OUT_BF16>(p.z, dst, acc);
     return;
   }
   part[y][threadIdx.x] = acc;
@@ -159,7 +172,7 @@ __global__ __launch_bounds__(HIER_BWD_LANES* HIER_BWD_PARTS) void hier_cat_bwd_k
   if (y == 0 && live) {
     f32x4_t sum = {0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < P; ++k) sum += part[k][threadIdx.x];
-    *(f32x4_t*)(p.z + dst) = sum;
+    hier_store_sum<OUT_BF16>(p.z, dst, sum);
   }
 }
 
@@ -330,12 +343,14 @@ extern "C" int vqx_upsample_cat_fwd(const vqx_hier_level* levels, int32_t n_leve
   return launch_status("vqx_upsample_cat_fwd");
 }
 
-extern "C" int vqx_upsample_cat_bwd(const vqx_hier_level* levels, int32_t n_levels, int32_t B, int32_t T,
-                                    const void* dout, int32_t ldo, int32_t dout_dtype, vqx_stream_t stream) {
+// Both backward entry points: the checks, the item table and the launch.
+static int hier_cat_bwd(const char* who, const vqx_hier_level* levels, int n_levels, int B, int T, const void* dout,
+                        int ldo, int dout_dtype, int level_dtype, vqx_stream_t stream) {
+  if (level_dtype != VQX_F32 && level_dtype != VQX_BF16) { set_error("%s: bad level_dtype %d", who, level_dtype); return -1; }
   HierLevels L;
   int total, longest;
   bool v8;
-  if (hier_prepare("vqx_upsample_cat_bwd", levels, n_levels, B, T, dout, ldo, dout_dtype, L, total, v8, longest)) return -1;
+  if (hier_prepare(who, levels, n_levels, B, T, dout, ldo, dout_dtype, L, total, v8, longest)) return -1;
   int64_t items = 0;
   for (int l = 0; l < n_levels; ++l) {
     L.start[l] = items;
@@ -343,12 +358,25 @@ extern "C" int vqx_upsample_cat_bwd(const vqx_hier_level* levels, int32_t n_leve
     items += (int64_t)B * L.T_l[l] * L.g0[l];
   }
   const int64_t grid = (items + HIER_BWD_LANES - 1) / HIER_BWD_LANES;
-  if (grid > INT32_MAX) { set_error("vqx_upsample_cat_bwd: %lld workgroups", (long long)grid); return -1; }
+  if (grid > INT32_MAX) { set_error("%s: %lld workgroups", who, (long long)grid); return -1; }
   const int P = longest >= HIER_LONG_SEG ? HIER_BWD_PARTS : 1;
   hipStream_t s = (hipStream_t)stream;
-  auto* fn = dout_dtype == VQX_BF16 ? hier_cat_bwd_kernel<true> : hier_cat_bwd_kernel<false>;
+  const bool bf = dout_dtype == VQX_BF16;
+  auto* fn = level_dtype == VQX_BF16 ? (bf ? hier_cat_bwd_kernel<true, true> : hier_cat_bwd_kernel<false, true>)
+                                     : (bf ? hier_cat_bwd_kernel<true, false> : hier_cat_bwd_kernel<false, false>);
   hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(HIER_BWD_LANES, P), 0, s, L, items, T, dout, (int64_t)ldo);
-  return launch_status("vqx_upsample_cat_bwd");
+  return launch_status(who);
+}
+
+extern "C" int vqx_upsample_cat_bwd(const vqx_hier_level* levels, int32_t n_levels, int32_t B, int32_t T,
+                                    const void* dout, int32_t ldo, int32_t dout_dtype, vqx_stream_t stream) {
+  return hier_cat_bwd("vqx_upsample_cat_bwd", levels, n_levels, B, T, dout, ldo, dout_dtype, VQX_F32, stream);
+}
+
+extern "C" int vqx_upsample_cat_bwd_to(const vqx_hier_level* levels, int32_t n_levels, int32_t B, int32_t T,
+                                       const void* dout, int32_t ldo, int32_t dout_dtype, int32_t level_dtype,
+                                       vqx_stream_t stream) {
+  return hier_cat_bwd("vqx_upsample_cat_bwd_to", levels, n_levels, B, T, dout, ldo, dout_dtype, level_dtype, stream);
 }
 
 extern "C" int vqx_codes_upsample_cat(const vqx_codes_level* levels, int32_t n_levels, int32_t B, int32_t T, void* out,

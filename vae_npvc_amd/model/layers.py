@@ -105,13 +105,12 @@ class ResSkipBlock(nn.Module):
         super().__init__()
         if (kernel_size - 1) % 2:
             raise ValueError("Not support even number kernel size.")  # layers.py:197
-        if not cond_channels:
-            raise NotImplementedError("decoder blocks without speaker conditioning (cond_channels 0)")
         wn = weight_norm
         self.conv_in = WNConv1d(channels, 2 * channels, kernel_size, transposed=True,
                                 padding=(kernel_size - 1) // 2 * dilation, dilation=dilation, weight_norm=wn)
         self.norm_layer = nn.GroupNorm(2, 2 * channels, eps=1e-5, affine=True)
-        self.conv_cond = WNConv1d(cond_channels, 2 * channels, 1, weight_norm=wn)
+        # cond_channels 0 / None: an unconditioned block, no conv_cond and no state_dict keys for it (layers.py:209-212)
+        self.conv_cond = WNConv1d(cond_channels, 2 * channels, 1, weight_norm=wn) if cond_channels else None
         self.res_skip_layers = WNConv1d(channels, channels + skip_channels, 1, weight_norm=wn)
         self.in_channels = channels
         self.dilation = dilation

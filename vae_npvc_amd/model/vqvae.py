@@ -119,6 +119,8 @@ class Model(nn.Module):
         super().__init__()
         self.encoder = Encoder(**arch["encoder"])
         self.decoder = Decoder(**arch["decoder"])
+        if not self.decoder.cond_ch:  # the fused engine always runs conv_cond; model/vqvae2.Decoder runs without
+            raise NotImplementedError("decoder blocks without speaker conditioning (cond_channels 0)")
         self.use_ema = arch.get("use_ema", False)
         # the reference's quantizers take any z_dim (layers_vq.py:166-173); the
         # fused VQ kernels (vqx_vq_forward) keep a frame's z_dim values in

@@ -183,9 +183,14 @@ class _Plan:
 
     def __init__(self, dec):
         self.dt = _DT[dec.compute_dtype]
-        self.steps, at = [], 0  # ("conv", _Conv) | ("block", conv_in, conv_cond, res_skip, at of gamma)
+        self.steps, at = [], 0  # ("conv", _Conv) | ("block", conv_in, conv_cond | None, res_skip, at of gamma)
         for layer in dec.layers:
             if isinstance(layer, ResSkipBlock):
+                if layer.conv_cond is None:  # unconditioned: 6 tensors per block
+                    ci, cc, rs = _Conv(layer.conv_in, at), None, _Conv(layer.res_skip_layers, at + 4)
+                    self.steps.append(("block", ci, cc, rs, at + 2))
+                    at += 6
+                    continue
                 ci, cc, rs = _Conv(layer.conv_in, at), _Conv(layer.conv_cond, at + 2), _Conv(layer.res_skip_layers, at + 6)
                 self.steps.append(("block", ci, cc, rs, at + 4))
                 at += 8
@@ -199,17 +204,19 @@ class _Plan:
         self.fin1, self.fin2 = _Conv(dec.final_layer[1], at), _Conv(dec.final_layer[3], at + 2)
         self.n_tensors = at + 4
         self.scale = math.sqrt(1.0 / len(dec.layers))
-        self.S, self.final, self.cond = dec.skip_ch, dec.final_ch, dec.cond_ch
+        self.S, self.final, self.cond = dec.skip_ch, dec.final_ch, dec.cond_ch or 0
 
     @staticmethod
     def tensors(dec):
         """The flat tensor list the plan indexes: per conv (w, bias), per block
-        conv_in, conv_cond, GroupNorm (gamma, beta), res_skip; then the final convs."""
+        conv_in, conv_cond (a conditioned block only), GroupNorm (gamma, beta), res_skip; then the final convs."""
         out = []
         for layer in dec.layers:
             if isinstance(layer, ResSkipBlock):
-                out += [layer.conv_in.effective_weight(), layer.conv_in.bias, layer.conv_cond.effective_weight(),
-                        layer.conv_cond.bias, layer.norm_layer.weight, layer.norm_layer.bias,
+                out += [layer.conv_in.effective_weight(), layer.conv_in.bias]
+                if layer.conv_cond is not None:
+                    out += [layer.conv_cond.effective_weight(), layer.conv_cond.bias]
+                out += [layer.norm_layer.weight, layer.norm_layer.bias,
                         layer.res_skip_layers.effective_weight(), layer.res_skip_layers.bias]
             else:
                 out += [layer.effective_weight(), layer.bias]
@@ -222,12 +229,16 @@ def _decoder_rows(plan, x2, B, T, rows, T_levels, ts):
     """The decoder's forward launches on frame-major operands: x2 [B*T, C] in
     the compute dtype, the conditioning levels `rows` (f32 [B*T_l, C_l]) and the
     flat tensor list `ts`.  Returns xhat f32 [B*T, final] and what the backward
-    reads (Tc, c_low, saved, wp, a_skip, f1, w1, w2)."""
+    reads (Tc, c_low, saved, wp, a_skip, f1, w1, w2).  An unconditioned plan
+    (plan.cond == 0) takes rows = None: no row bias in the conv_in GEMMs, no
+    conv_cond launches; Tc and c_low are None."""
     dev, dt = x2.device, plan.dt
     N = B * T
     e = functools.partial(torch.empty, device=dev)
     # conditioning at its own rate: c_low [B*Tc, cond] f32
-    if T_levels:
+    if not plan.cond:
+        Tc, c_low = None, None
+    elif T_levels:
         Tc = choose_tc(T, T_levels)
         c_low = ops.upsample_cat_fwd(rows, B, Tc, e(B * Tc, plan.cond, dtype=F32))
     else:
@@ -248,12 +259,14 @@ def _decoder_rows(plan, x2, B, T, rows, T_levels, ts):
         _, ci, cc, rs, ag = st
         C = ci.cin
         w_in, w_rs = _pack(ts[ci.at], True, dt), _pack(ts[rs.at], False, dt)
-        w_cc = _pack(ts[cc.at], False, F32)
-        wp[ci.at], wp[cc.at], wp[rs.at] = w_in, w_cc, w_rs
-        P = e(B * Tc, 2 * C, dtype=F32)  # conv_cond(c) + its bias, one row per conditioning frame
-        _fwd(cc, c_low, w_cc, P, Tc, bias=ts[cc.at + 1])
+        wp[ci.at], wp[rs.at] = w_in, w_rs
+        seg = {}
+        if cc is not None:
+            w_cc = wp[cc.at] = _pack(ts[cc.at], False, F32)
+            P = e(B * Tc, 2 * C, dtype=F32)  # conv_cond(c) + its bias, one row per conditioning frame
+            _fwd(cc, c_low, w_cc, P, Tc, bias=ts[cc.at + 1])
+            seg = dict(rowbias=P, rowbias_T=Tc if Tc > 1 else 0)
         u, g, mr = e(N, 2 * C, dtype=dt), e(N, C, dtype=dt), e(B, 2, 2, dtype=F32)
-        seg = dict(rowbias=P, rowbias_T=Tc if Tc > 1 else 0)
         if T % 128 == 0 and C % 128 == 0:  # GroupNorm statistics from the GEMM's epilogue tiles
             gst = e((N // 128) * (2 * C // 128) * 4, dtype=F32)
             _fwd(ci, cur, w_in, u, T, bias=ts[ci.at + 1], gn_stats=gst, gn_groups=2, **seg)
@@ -276,16 +289,101 @@ def _decoder_rows(plan, x2, B, T, rows, T_levels, ts):
     return xhat, (Tc, c_low, saved, wp, a_skip, f1, w1, w2)
 
 
+def _decoder_rows_bwd(plan, B, T, Tc, keep, dxhat):
+    """The decoder's backward launches on frame-major operands: `keep` =
+    (saved, wp, a_skip, f1, c_low, ts) as _decoder_rows left them (wp with the
+    final convs' packed weights added), dxhat [B*T, final] the output gradient
+    in the compute dtype.  Returns (dx f32 [B*T, C_in], dc f32 [B*Tc, cond] the
+    gradient of c_low or None for an unconditioned plan, grads: dL/d(ts) in the
+    plan's order)."""
+    saved, wp, a_skip, f1, c_low, ts = keep
+    dev, dt, S = dxhat.device, plan.dt, plan.S
+    N = B * T
+    e = functools.partial(torch.empty, device=dev)
+    grads = [None] * plan.n_tensors
+    Cmax = max(st[1].cin for st in plan.steps if st[0] == "block")
+    cs_part = e(64 * max(2 * Cmax, Cmax + S, plan.final, plan.cond, 1024), dtype=F32)
+    gnb_part = e(B * 64 * 2, dtype=F32)
+    # final layer: ReLU, conv, ReLU, conv on scale * sum(skips)
+    f1c, f2c = plan.fin1, plan.fin2
+    grads[f2c.at + 1] = _colsum(dxhat, cs_part)
+    grads[f2c.at] = _wgrad(f2c, dxhat, f1, T)
+    df1 = e(N, f2c.cin, dtype=dt)
+    _dgrad(f2c, dxhat, wp[f2c.at], df1, T, mask=f1, mask_slope=0.0)
+    grads[f1c.at + 1] = _colsum(df1, cs_part)
+    grads[f1c.at] = _wgrad(f1c, df1, a_skip, T)
+    # dr: [dL/dx | dL/dskip] of the current block's output, two buffers per width in turn
+    bufs = {}
+
+    def dr(C, k):
+        if (C, k) not in bufs:
+            bufs[(C, k)] = e(N, C + S, dtype=dt)
+            if (C, k) != first_key:
+                ops.convert_2d(bufs[first_key][:, first_key[0]:], bufs[(C, k)][:, C:])
+        return bufs[(C, k)]
+
+    C_last = plan.steps[-1][1].cin
+    first_key = (C_last, 0)
+    cur = dr(C_last, 0)
+    _dgrad(f1c, df1, wp[f1c.at], cur[:, C_last:], T, mask=a_skip, mask_slope=0.0, mask_scale=plan.scale)
+    ops.convert_2d(None, cur, cols=C_last)  # dL/dx at the decoder output is 0: the last residual is unused
+    k, dc, dx = 0, None, None
+    for st, sv in zip(reversed(plan.steps), reversed(saved)):
+        if st[0] == "conv":
+            cv = st[1]
+            cur_x = cur[:, :cv.cout]
+            grads[cv.at + 1] = _colsum(cur_x, cs_part)
+            grads[cv.at] = _wgrad(cv, cur_x, sv[0], T)
+            if sv[0] is saved[0][0]:  # the decoder input
+                dx = e(N, cv.cin, dtype=F32)
+                _dgrad(cv, cur_x, wp[cv.at], dx, T, out_f32=True)
+            else:
+                k ^= 1
+                nxt = dr(cv.cin, k)
+                _dgrad(cv, cur_x, wp[cv.at], nxt[:, :cv.cin], T)
+                cur = nxt
+            continue
+        _, ci, cc, rs, ag = st
+        xin, u, g, mr = sv
+        C = ci.cin
+        grads[rs.at + 1] = _colsum(cur, cs_part)
+        grads[rs.at] = _wgrad(rs, cur, g, T)
+        dg, du = e(N, C, dtype=dt), e(N, 2 * C, dtype=dt)
+        _dgrad(rs, cur, wp[rs.at], dg, T)
+        cs_b, dgam_b, dbet_b = (e(B, 2 * C, dtype=F32) for _ in range(3))
+        ops.gn_bwd(dg, u, du, T, 2, True, mr, ts[ag], ts[ag + 1], gnb_part, cs_b, dgam_b, dbet_b)
+        grads[ci.at + 1] = _colsum(cs_b, cs_part)
+        grads[ag], grads[ag + 1] = _colsum(dgam_b, cs_part), _colsum(dbet_b, cs_part)
+        # conditioning: dP = the per-segment sums of du, then conv_cond's own gradients at the low rate
+        if cc is not None:
+            if Tc == 1:
+                dP = cs_b
+            else:
+                dP = e(B * Tc, 2 * C, dtype=F32)
+                ops.upsample_cat_bwd([dP], B, T, du)
+            grads[cc.at + 1] = grads[ci.at + 1] if Tc == 1 else _colsum(dP, cs_part)
+            grads[cc.at] = _wgrad(cc, dP, c_low, Tc)
+            dc_new = e(B * Tc, plan.cond, dtype=F32)
+            _dgrad(cc, dP, wp[cc.at], dc_new, Tc, **({} if dc is None else dict(res=dc)))
+            dc = dc_new
+        grads[ci.at] = _wgrad(ci, du, xin, T)
+        k ^= 1
+        nxt = dr(C, k)
+        _dgrad(ci, du, wp[ci.at], nxt[:, :C], T, res=cur[:, :C])
+        cur = nxt
+    return dx, dc, grads
+
+
 class _DecoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, save, T_levels, x, *rest):
-        nl = max(1, len(T_levels))
+        nl = max(1, len(T_levels)) if plan.cond else 0
         cin, ts = rest[:nl], rest[nl:]
         if not x.is_cuda or not all(t.is_cuda for t in rest):
             raise L.VqxError("vqvae2.Decoder runs on the MI355X only (libvqx); move it and its inputs with .cuda()")
         B, _, T = x.shape
         ts = [t.detach().float() for t in ts]
-        rows = [_to_rows(z) for z in cin]
+        rows = [_to_rows(z) for z in cin] if plan.cond else None
         x2 = torch.empty(B * T, x.shape[1], device=x.device, dtype=plan.dt)
         ops.nct_to_ntc(x.float().contiguous(), x2)
         xhat, (Tc, c_low, saved, wp, a_skip, f1, w1, w2) = _decoder_rows(plan, x2, B, T, rows, T_levels, ts)
@@ -300,84 +398,14 @@ class _DecoderFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dout):
         plan, (B, T), Tc = ctx.plan, ctx.dims, ctx.Tc
-        saved, wp, a_skip, f1, c_low, ts = ctx.keep
-        dev, dt, S = dout.device, plan.dt, plan.S
-        N = B * T
-        e = functools.partial(torch.empty, device=dev)
-        grads = [None] * plan.n_tensors
-        Cmax = max(st[1].cin for st in plan.steps if st[0] == "block")
-        cs_part = e(64 * max(2 * Cmax, Cmax + S, plan.final, plan.cond, 1024), dtype=F32)
-        gnb_part = e(B * 64 * 2, dtype=F32)
-        # final layer: ReLU, conv, ReLU, conv on scale * sum(skips)
-        dxhat = e(N, plan.final, dtype=dt)
+        dxhat = torch.empty(B * T, plan.final, device=dout.device, dtype=plan.dt)
         ops.nct_to_ntc(dout.float().contiguous(), dxhat)
-        f1c, f2c = plan.fin1, plan.fin2
-        grads[f2c.at + 1] = _colsum(dxhat, cs_part)
-        grads[f2c.at] = _wgrad(f2c, dxhat, f1, T)
-        df1 = e(N, f2c.cin, dtype=dt)
-        _dgrad(f2c, dxhat, wp[f2c.at], df1, T, mask=f1, mask_slope=0.0)
-        grads[f1c.at + 1] = _colsum(df1, cs_part)
-        grads[f1c.at] = _wgrad(f1c, df1, a_skip, T)
-        # dr: [dL/dx | dL/dskip] of the current block's output, two buffers per width in turn
-        bufs = {}
-
-        def dr(C, k):
-            if (C, k) not in bufs:
-                bufs[(C, k)] = e(N, C + S, dtype=dt)
-                if (C, k) != first_key:
-                    ops.convert_2d(bufs[first_key][:, first_key[0]:], bufs[(C, k)][:, C:])
-            return bufs[(C, k)]
-
-        C_last = plan.steps[-1][1].cin
-        first_key = (C_last, 0)
-        cur = dr(C_last, 0)
-        _dgrad(f1c, df1, wp[f1c.at], cur[:, C_last:], T, mask=a_skip, mask_slope=0.0, mask_scale=plan.scale)
-        ops.convert_2d(None, cur, cols=C_last)  # dL/dx at the decoder output is 0: the last residual is unused
-        k, dc, dx = 0, None, None
-        for st, sv in zip(reversed(plan.steps), reversed(saved)):
-            if st[0] == "conv":
-                cv = st[1]
-                cur_x = cur[:, :cv.cout]
-                grads[cv.at + 1] = _colsum(cur_x, cs_part)
-                grads[cv.at] = _wgrad(cv, cur_x, sv[0], T)
-                if sv[0] is saved[0][0]:  # the decoder input
-                    dx = e(N, cv.cin, dtype=F32)
-                    _dgrad(cv, cur_x, wp[cv.at], dx, T, out_f32=True)
-                else:
-                    k ^= 1
-                    nxt = dr(cv.cin, k)
-                    _dgrad(cv, cur_x, wp[cv.at], nxt[:, :cv.cin], T)
-                    cur = nxt
-                continue
-            _, ci, cc, rs, ag = st
-            xin, u, g, mr = sv
-            C = ci.cin
-            grads[rs.at + 1] = _colsum(cur, cs_part)
-            grads[rs.at] = _wgrad(rs, cur, g, T)
-            dg, du = e(N, C, dtype=dt), e(N, 2 * C, dtype=dt)
-            _dgrad(rs, cur, wp[rs.at], dg, T)
-            cs_b, dgam_b, dbet_b = (e(B, 2 * C, dtype=F32) for _ in range(3))
-            ops.gn_bwd(dg, u, du, T, 2, True, mr, ts[ag], ts[ag + 1], gnb_part, cs_b, dgam_b, dbet_b)
-            grads[ci.at + 1] = _colsum(cs_b, cs_part)
-            grads[ag], grads[ag + 1] = _colsum(dgam_b, cs_part), _colsum(dbet_b, cs_part)
-            # conditioning: dP = the per-segment sums of du, then conv_cond's own gradients at the low rate
-            if Tc == 1:
-                dP = cs_b
-            else:
-                dP = e(B * Tc, 2 * C, dtype=F32)
-                ops.upsample_cat_bwd([dP], B, T, du)
-            grads[cc.at + 1] = grads[ci.at + 1] if Tc == 1 else _colsum(dP, cs_part)
-            grads[cc.at] = _wgrad(cc, dP, c_low, Tc)
-            dc_new = e(B * Tc, plan.cond, dtype=F32)
-            _dgrad(cc, dP, wp[cc.at], dc_new, Tc, **({} if dc is None else dict(res=dc)))
-            dc = dc_new
-            grads[ci.at] = _wgrad(ci, du, xin, T)
-            k ^= 1
-            nxt = dr(C, k)
-            _dgrad(ci, du, wp[ci.at], nxt[:, :C], T, res=cur[:, :C])
-            cur = nxt
+        dx, dc, grads = _decoder_rows_bwd(plan, B, T, Tc, ctx.keep, dxhat)
+        e = functools.partial(torch.empty, device=dout.device)
         # the conditioning's gradient back to the levels (or to the tensor c)
-        if ctx.T_levels:
+        if dc is None:
+            dcin = []
+        elif ctx.T_levels:
             dl = [e(B * Tl, Cl, dtype=F32) for _, Cl, Tl in ctx.level_shapes]
             ops.upsample_cat_bwd(dl, B, Tc, dc)
             dcin = [_to_nct(d, B, s[2]) for d, s in zip(dl, ctx.level_shapes)]
@@ -389,7 +417,11 @@ class _DecoderFn(torch.autograd.Function):
 
 class Decoder(_Decoder):
     """vqvae2.py:274-371 with `compute_dtype: fp32|bf16`; forward((x, c)) with c a
-    (B, cond, T) tensor or a list of levels (B, C_l, T_l), sum C_l == cond."""
+    (B, cond, T) tensor or a list of levels (B, C_l, T_l), sum C_l == cond.
+    With cond_channels 0 / None the blocks own no conv_cond (layers.py:209-212)
+    and the call is forward((x, None)): no row bias in the conv_in GEMMs, no
+    conv_cond launches or gradients.  A conditioning given to such a decoder, or
+    None given to a conditioned one, is a ValueError."""
 
     def __init__(self, *args, compute_dtype="fp32", **kw):
         scales = kw.get("upsample_scales", args[2] if len(args) > 2 else (1, 1, 1, 1))
@@ -407,6 +439,17 @@ class Decoder(_Decoder):
         if x.dim() != 3:
             raise ValueError(f"vqvae2.Decoder: x {tuple(x.shape)} is not (B, C, T)")
         B, _, T = x.shape
+        if not self.cond_ch:  # unconditioned (cond_channels 0 / None): forward((x, None))
+            if c is not None:
+                raise ValueError("vqvae2.Decoder: this decoder is unconditioned (cond_channels 0); it takes (x, None) "
+                                 "and would ignore the conditioning it was given")
+            if self._plan is None:
+                self._plan = _Plan(self)
+            ts = _Plan.tensors(self)
+            save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, *ts))
+            return _DecoderFn.apply(self._plan, save, (), x, *ts)
+        if c is None:
+            raise ValueError(f"vqvae2.Decoder: the conditioning is None, this decoder has cond_channels {self.cond_ch}")
         levels = [c] if torch.is_tensor(c) else list(c)
         if not levels or any(z.dim() != 3 or z.shape[0] != B for z in levels) \
                 or sum(z.shape[1] for z in levels) != self.cond_ch:
@@ -438,7 +481,13 @@ class Decoder(_Decoder):
         if not x_rows.is_cuda or x_rows.dim() != 2 or x_rows.dtype != plan.dt or x_rows.stride(1) != 1 \
                 or x_rows.shape[0] != B * T:
             raise ValueError(f"vqvae2.Decoder: x_rows must be device [{B * T}, C] rows in {plan.dt}")
-        if any(r.dim() != 2 or r.dtype != F32 or r.shape[0] % B for r in cond_rows) \
+        if not self.cond_ch:
+            if cond_rows is not None:
+                raise ValueError("vqvae2.Decoder: this decoder is unconditioned (cond_channels 0); cond_rows must be None")
+            with torch.no_grad():
+                ts = [t.detach().float() for t in _Plan.tensors(self)]
+                return _decoder_rows(plan, x_rows, B, T, None, (), ts)[0]
+        if cond_rows is None or any(r.dim() != 2 or r.dtype != F32 or r.shape[0] % B for r in cond_rows) \
                 or sum(r.shape[1] for r in cond_rows) != self.cond_ch:
             raise ValueError(f"vqvae2.Decoder: the conditioning must be f32 [B*T_l, C_l] rows with sum C_l == "
                              f"{self.cond_ch}")

@@ -1102,15 +1102,15 @@ def gst_bwd(z, T, params, heads, d_style, ws, dz, grads):
 HIER_MAX_LEVELS = 8  # include/vqx.h vqx_upsample_cat_*
 
 
-def _hier_levels(levels, B, what):
-    """vqx_hier_level array of frame-major f32 levels [B*T_l, C_l] (rows of stride(0))."""
+def _hier_levels(levels, B, what, dtype=torch.float32):
+    """vqx_hier_level array of frame-major levels [B*T_l, C_l] of `dtype` (rows of stride(0))."""
     if not 1 <= len(levels) <= HIER_MAX_LEVELS:
         raise ValueError(f"{what}: {len(levels)} levels, 1..{HIER_MAX_LEVELS} are supported")
     _check_cuda(*levels)
     arr = (L.HierLevel * len(levels))()
     for e, z in zip(arr, levels):
-        if z.dtype != torch.float32 or z.dim() != 2 or z.stride(1) != 1 or z.shape[0] % B:
-            raise ValueError(f"{what}: a level must be f32 [B*T_l, C_l] rows with unit column stride")
+        if z.dtype != dtype or z.dim() != 2 or z.stride(1) != 1 or z.shape[0] % B:
+            raise ValueError(f"{what}: a level must be {dtype} [B*T_l, C_l] rows with unit column stride")
         e.z, e.T_l, e.C, e.ld = ptr(z), z.shape[0] // B, z.shape[1], z.stride(0)
         _rows(z, z.shape[0], e.ld, e.C, f"{what} level")
     return arr
@@ -1139,6 +1139,22 @@ def upsample_cat_bwd(dlevels, B, T, dout):
         raise ValueError(f"upsample_cat_bwd: dout must be [{B * T}, C] rows with unit column stride")
     _rows(dout, dout.shape[0], dout.stride(0), sum(z.shape[1] for z in dlevels), "upsample_cat_bwd dout")
     call("vqx_upsample_cat_bwd", arr, len(dlevels), B, T, ptr(dout), dout.stride(0), dt_code(dout.dtype), stream_ptr())
+    return dlevels
+
+
+def upsample_cat_bwd_to(dlevels, B, T, dout):
+    """upsample_cat_bwd with the levels stored in their own dtype (all f32 or
+    all bf16; vqx_upsample_cat_bwd_to): the same fp32 sums in the same order,
+    rounded once to nearest even for bf16 levels."""
+    if not dlevels or any(z.dtype != dlevels[0].dtype for z in dlevels):
+        raise ValueError("upsample_cat_bwd_to: the levels must share one dtype")
+    arr = _hier_levels(dlevels, B, "upsample_cat_bwd_to", dlevels[0].dtype)
+    _check_cuda(dout)
+    if dout.dim() != 2 or dout.shape[0] != B * T or dout.stride(1) != 1:
+        raise ValueError(f"upsample_cat_bwd_to: dout must be [{B * T}, C] rows with unit column stride")
+    _rows(dout, dout.shape[0], dout.stride(0), sum(z.shape[1] for z in dlevels), "upsample_cat_bwd_to dout")
+    call("vqx_upsample_cat_bwd_to", arr, len(dlevels), B, T, ptr(dout), dout.stride(0), dt_code(dout.dtype),
+         dt_code(dlevels[0].dtype), stream_ptr())
     return dlevels
 
 
