@@ -958,6 +958,54 @@ int vqx_nct_to_ntc_keep(const float* g_nct, int32_t B, int32_t C, int32_t T, con
 int vqx_vq_commit_bwd_g(const float* z, const float* zq, int32_t B, int32_t D, int32_t T, float s, const float* g,
                         int32_t nct, float* dz, vqx_stream_t stream);
 
+/*
+ * A batch of different lengths (the hierarchical model's batched conversion,
+ * forward only): frame-major rows [B*T][ld] in which utterance b owns rows
+ * t < len[b], 1 <= len[b] <= T.  `len` (and n_len / m_len) are HOST arrays:
+ * they are checked item by item before the first launch (a failure names the
+ * item in vqx_last_error() and launches nothing) and travel to the kernels by
+ * value in the kernel arguments, 896 utterances a launch (96 for the
+ * concatenation), so there is no device table, copy, allocation or
+ * synchronisation.  n_rows = B*T < 2^31.  dtype VQX_F32 | VQX_BF16; pointers
+ * 16-B aligned, channel counts and strides multiples of a 16-byte chunk (4 f32
+ * / 8 bf16).  No atomics: equal arguments give equal bits.  Additive: the ABI
+ * version does not change.
+ *
+ * vqx_groupnorm_stats_len: vqx_groupnorm_stats over rows t < len[b] only
+ *   (G = 1 or 2; two passes per row part, the 8 parts merged in order in
+ *   double); partials >= B*G*24 floats, mean_rstd [B][G][2] as the plain call.
+ * vqx_gn_lrelu_fwd_len / vqx_gn_glu_fwd_len: vqx_gn_lrelu_fwd / vqx_gn_glu_fwd
+ *   on rows t < len[b] (the same bits as the plain call on those rows); rows
+ *   t >= len[b] of g are written as zeros and not read.
+ * vqx_mask_tail: x[b*T + t][0..C) = 0 for len[b] <= t < T, in place; nothing
+ *   else is read or written.
+ * vqx_codes_upsample_cat_len: vqx_codes_upsample_cat with per-utterance
+ *   lengths.  Level l is stored with its own padded T_l (levels[l].T_l);
+ *   utterance b has target length n_len[b] <= T and level lengths
+ *   m_len[b*n_levels + l], 1 <= m <= min(n_len[b], T_l):
+ *     out[b*T + t][off_l + c] = level_l[b][min(t / (n_b / m), m - 1)][c], t < n_b
+ *   and zeros over [0, sum C_l) for t >= n_b.  Index entries at t >= m are
+ *   never read.
+ * vqx_segment_mean: out[b][c] = (sum_{t < len[b]} z[b*T + t][c]) / len[b], f32
+ *   z [B*T][ldz] -> out [B][ldo], summed in a fixed order.
+ */
+int vqx_groupnorm_stats_len(const void* x, int32_t ldx, int32_t dtype, int64_t n_rows, int32_t T, int32_t C,
+                            int32_t G, const int32_t* len, float eps, float* partials, float* mean_rstd,
+                            vqx_stream_t stream);
+int vqx_gn_lrelu_fwd_len(const void* h, int32_t ldh, void* g, int32_t ldg, int32_t dtype, int64_t n_rows, int32_t T,
+                         int32_t C, const int32_t* len, const float* mean_rstd, const float* gamma, const float* beta,
+                         vqx_stream_t stream);
+int vqx_gn_glu_fwd_len(const void* u, int32_t ldu, void* g, int32_t ldg, int32_t dtype, int64_t n_rows, int32_t T,
+                       int32_t C, const int32_t* len, const float* mean_rstd, const float* gamma, const float* beta,
+                       vqx_stream_t stream);
+int vqx_mask_tail(void* x, int32_t ldx, int32_t dtype, int64_t n_rows, int32_t T, int32_t C, const int32_t* len,
+                  vqx_stream_t stream);
+int vqx_codes_upsample_cat_len(const vqx_codes_level* levels, int32_t n_levels, int32_t B, int32_t T,
+                               const int32_t* n_len, const int32_t* m_len, void* out, int32_t ldo, int32_t out_dtype,
+                               vqx_stream_t stream);
+int vqx_segment_mean(const float* z, int32_t ldz, int64_t n_rows, int32_t T, int32_t C, const int32_t* len,
+                     float* out, int32_t ldo, vqx_stream_t stream);
+
 /* ABI 130: vqx_conv_args.rowbias_T appended (segmented row bias of the forward
  * epilogue; 0 or 1 keeps every earlier call's bits) and vqx_upsample_cat_*. */
 /* ABI version (major*100 + minor); VQX_ABI_VERSION is what this header describes. */

@@ -217,6 +217,17 @@ _SIGS = {
                                 c_int32, c_void_p],
     "vqx_codes_upsample_cat": [ctypes.POINTER(CodesLevel), c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
                                c_void_p],
+    # a batch of different lengths: `len` arguments are host int32 arrays
+    "vqx_groupnorm_stats_len": [c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_void_p, c_float,
+                                c_void_p, c_void_p, c_void_p],
+    "vqx_gn_lrelu_fwd_len": [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p],
+    "vqx_gn_glu_fwd_len": [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_void_p],
+    "vqx_mask_tail": [c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p],
+    "vqx_codes_upsample_cat_len": [ctypes.POINTER(CodesLevel), c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                   c_int32, c_int32, c_void_p],
+    "vqx_segment_mean": [c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p],
     "vqx_ntc_to_nct_scale": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p],
     "vqx_nct_to_ntc_lrelu_bwd": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float, c_void_p,
                                  c_int32, c_int32, c_void_p],

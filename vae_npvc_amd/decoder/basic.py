@@ -38,6 +38,8 @@ class Decoder(object):
             return self.model.infer((feat, spk))
 
     def decode(self, decode_dir, output_dir, compress=True):
+        if getattr(self, "decode_batch_size", 1) > 1:  # a subclass that converts padded batches (decoder.hier)
+            return self.decode_batched(decode_dir, output_dir, compress=compress)
         decode_dir = Path(decode_dir)
         output_dir = str(output_dir)
         for file in ["trials", "feats.scp"]:

@@ -225,14 +225,25 @@ class _Plan:
         return out
 
 
-def _decoder_rows(plan, x2, B, T, rows, T_levels, ts):
+def _decoder_rows(plan, x2, B, T, rows, T_levels, ts, lengths=None):
     """The decoder's forward launches on frame-major operands: x2 [B*T, C] in
     the compute dtype, the conditioning levels `rows` (f32 [B*T_l, C_l]) and the
     flat tensor list `ts`.  Returns xhat f32 [B*T, final] and what the backward
     reads (Tc, c_low, saved, wp, a_skip, f1, w1, w2).  An unconditioned plan
     (plan.cond == 0) takes rows = None: no row bias in the conv_in GEMMs, no
-    conv_cond launches; Tc and c_low are None."""
+    conv_cond launches; Tc and c_low are None.
+
+    lengths (forward only): utterance b owns rows t < lengths[b] of the padded
+    T.  x2 must hold zeros in the other rows, the conditioning is one row per
+    utterance or already at full rate (a per-utterance stretch is the caller's,
+    vqx_codes_upsample_cat_len).  The GroupNorm statistics run over the valid
+    rows (the *_len kernels, never the GEMM tiles), every operand of a conv
+    with more than one tap is given a zero tail (ops.mask_tail after the GEMM
+    that wrote it), and xhat comes back with zero tails."""
     dev, dt = x2.device, plan.dt
+    lens = None if lengths is None else ops.len_array(lengths, B, "vqvae2.Decoder lengths")
+    if lens is not None and plan.cond and T_levels and choose_tc(T, T_levels) not in (1, T):
+        raise ValueError("vqvae2.Decoder: with lengths the conditioning is one row per utterance or full rate")
     N = B * T
     e = functools.partial(torch.empty, device=dev)
     # conditioning at its own rate: c_low [B*Tc, cond] f32
@@ -253,6 +264,8 @@ def _decoder_rows(plan, x2, B, T, rows, T_levels, ts):
             w = wp[cv.at] = _pack(ts[cv.at], cv.transposed, dt)
             y = e(N, cv.cout, dtype=dt)
             _fwd(cv, cur, w, y, T, bias=ts[cv.at + 1])
+            if lens is not None:
+                ops.mask_tail(y, T, lens)
             saved.append((cur,))
             cur = y
             continue
@@ -267,7 +280,11 @@ def _decoder_rows(plan, x2, B, T, rows, T_levels, ts):
             _fwd(cc, c_low, w_cc, P, Tc, bias=ts[cc.at + 1])
             seg = dict(rowbias=P, rowbias_T=Tc if Tc > 1 else 0)
         u, g, mr = e(N, 2 * C, dtype=dt), e(N, C, dtype=dt), e(B, 2, 2, dtype=F32)
-        if T % 128 == 0 and C % 128 == 0:  # GroupNorm statistics from the GEMM's epilogue tiles
+        if lens is not None:  # statistics and apply over each utterance's own rows; g gets a zero tail
+            _fwd(ci, cur, w_in, u, T, bias=ts[ci.at + 1], **seg)
+            ops.groupnorm_stats_len(u, T, 2, lens, gn_part, mr)
+            ops.gn_glu_fwd_len(u, g, T, lens, mr, ts[ag], ts[ag + 1])
+        elif T % 128 == 0 and C % 128 == 0:  # GroupNorm statistics from the GEMM's epilogue tiles
             gst = e((N // 128) * (2 * C // 128) * 4, dtype=F32)
             _fwd(ci, cur, w_in, u, T, bias=ts[ci.at + 1], gn_stats=gst, gn_groups=2, **seg)
             ops.gn_glu_fwd_tiles(u, g, T, gst, mr, ts[ag], ts[ag + 1])
@@ -277,6 +294,8 @@ def _decoder_rows(plan, x2, B, T, rows, T_levels, ts):
             ops.gn_glu_fwd(u, g, T, mr, ts[ag], ts[ag + 1])
         y = e(N, C, dtype=dt)
         _fwd(rs, g, w_rs, y, T, bias=ts[rs.at + 1], res=cur, out2=skip32, split_col=C, out2_accumulate=not first)
+        if lens is not None:  # the residual is the next conv_in's operand; its tail holds the bias
+            ops.mask_tail(y, T, lens)
         first = False
         saved.append((cur, u, g, mr))
         cur = y
@@ -284,8 +303,14 @@ def _decoder_rows(plan, x2, B, T, rows, T_levels, ts):
     xhat = e(N, plan.final, dtype=F32)
     ops.scale_act_2d(skip32, a_skip, plan.scale, L.PRO_RELU)
     w1, w2 = _pack(ts[plan.fin1.at], False, dt), _pack(ts[plan.fin2.at], False, dt)
+    if lens is not None and plan.fin1.k > 1:
+        ops.mask_tail(a_skip, T, lens)
     _fwd(plan.fin1, a_skip, w1, f1, T, bias=ts[plan.fin1.at + 1], act=L.PRO_RELU)
+    if lens is not None and plan.fin2.k > 1:
+        ops.mask_tail(f1, T, lens)
     _fwd(plan.fin2, f1, w2, xhat, T, bias=ts[plan.fin2.at + 1], out_f32=True)
+    if lens is not None:
+        ops.mask_tail(xhat, T, lens)
     return xhat, (Tc, c_low, saved, wp, a_skip, f1, w1, w2)
 
 
@@ -469,12 +494,18 @@ class Decoder(_Decoder):
         save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, *levels, *ts))
         return _DecoderFn.apply(self._plan, save, T_levels, x, *levels, *ts)
 
-    def forward_rows(self, x_rows, B, T, cond_rows):
+    def forward_rows(self, x_rows, B, T, cond_rows, lengths=None):
         """forward without gradients on frame-major operands: x_rows [B*T, C] in
         the compute dtype (as vqx_codes_upsample_cat writes it) in place of
         (B, C, T), so the first layout change is skipped; cond_rows the
         conditioning levels as f32 [B*T_l, C_l] rows.  Returns xhat f32
-        [B*T, final] rows.  Nothing is kept for a backward."""
+        [B*T, final] rows.  Nothing is kept for a backward.  lengths: host
+        ints, utterance b owns rows t < lengths[b] (x_rows zero elsewhere, the
+        conditioning one row per utterance or full rate; _decoder_rows)."""
+        if lengths is not None:
+            lengths = ops.len_array(lengths, B, "vqvae2.Decoder lengths")
+            if any(not 1 <= n <= T for n in lengths):
+                raise ValueError(f"vqvae2.Decoder: lengths must lie in 1..T = {T}")
         if self._plan is None:
             self._plan = _Plan(self)
         plan = self._plan
@@ -486,7 +517,7 @@ class Decoder(_Decoder):
                 raise ValueError("vqvae2.Decoder: this decoder is unconditioned (cond_channels 0); cond_rows must be None")
             with torch.no_grad():
                 ts = [t.detach().float() for t in _Plan.tensors(self)]
-                return _decoder_rows(plan, x_rows, B, T, None, (), ts)[0]
+                return _decoder_rows(plan, x_rows, B, T, None, (), ts, lengths)[0]
         if cond_rows is None or any(r.dim() != 2 or r.dtype != F32 or r.shape[0] % B for r in cond_rows) \
                 or sum(r.shape[1] for r in cond_rows) != self.cond_ch:
             raise ValueError(f"vqvae2.Decoder: the conditioning must be f32 [B*T_l, C_l] rows with sum C_l == "
@@ -496,7 +527,9 @@ class Decoder(_Decoder):
             src_index(T, Tl)
         with torch.no_grad():
             ts = [t.detach().float() for t in _Plan.tensors(self)]
-            return _decoder_rows(plan, x_rows, B, T, list(cond_rows), T_levels, ts)[0]
+            if lengths is not None and T_levels == (T,):
+                T_levels = ()  # already at full rate: read in place
+            return _decoder_rows(plan, x_rows, B, T, list(cond_rows), T_levels, ts, lengths)[0]
 
 
 # ------------------------------------------------------------------ encoder
@@ -577,7 +610,7 @@ def _total_scale(enc):
     return math.prod(getattr(enc.encode[i], "scale", 1) for i in enc.stage_index)
 
 
-def _encoder_rows(plan, inp, B, T, ts, ragged=False):
+def _encoder_rows(plan, inp, B, T, ts, ragged=False, lengths=None):
     """The encoder's forward launches on the frame-major input `inp` [B*T, C_in]
     in the compute dtype.  Returns z f32 [B*T', z], feat [B*T', C] (the last
     stage's LeakyReLU, compute dtype), T', and what the backward reads (saved, wp).
@@ -587,11 +620,24 @@ def _encoder_rows(plan, inp, B, T, ts, ragged=False):
     to (J+1)*s rows, as J+1 folded frames, and its first floor((T_in + 2p - 2s)/s)
     + 1 output rows are kept (J for an even s).  Every kept row reads real frames
     or zeros where the strided conv reads its own padding, so this is exact; the
-    layers after it see the kept rows alone."""
+    layers after it see the kept rows alone.
+
+    lengths (any B, nothing kept for a backward): utterance b owns rows
+    t < lengths[b] of the padded T, a multiple of the total stride, and `inp`
+    holds zeros in the other rows.  A stage keeps _stage_frames(len, s) frames
+    per utterance: the zero tail gives a partial last group the zeros the
+    strided conv reads from its own padding (the argument above, for every
+    utterance).  The GroupNorm statistics run over the valid rows (the *_len
+    kernels, never the GEMM tiles) and every LeakyReLU output a 3-tap conv reads
+    is given a zero tail (ops.mask_tail).  z and feat keep the padded T'; the
+    tail rows of z are not defined."""
     dev, dt = inp.device, plan.dt
     e = functools.partial(torch.empty, device=dev)
     gn_part = e(B * 2 * 24, dtype=F32)
     wp, saved, T_in = {}, [], T
+    lens = None if lengths is None else list(ops.len_array(lengths, B, "vqvae2.Encoder lengths"))
+    if lens is not None and T % plan.total_scale:
+        raise ValueError(f"vqvae2.Encoder: with lengths the padded T = {T} must be a multiple of {plan.total_scale}")
     for conv, blocks in plan.stages:
         s, C = conv.scale, conv.cout
         Ts = T_in // s
@@ -622,7 +668,11 @@ def _encoder_rows(plan, inp, B, T, ts, ragged=False):
             ops.conv_fwd(inp.view(B * Tf, s * conv.cin), w, c, T=Tf, cin=s * conv.cin, cout=C, ntaps=3, pad=1,
                          bias=ts[conv.at + 1], act=L.PRO_LRELU, y2=a)
             c, a = c[:N], a[:N]
-        fuse = Ts % 128 == 0 and C % 128 == 0  # GroupNorm statistics from the GEMM's epilogue tiles
+        if lens is not None:
+            lens = [_stage_frames(n, s) for n in lens]
+            ops.mask_tail(a, Ts, lens)
+        # GroupNorm statistics from the GEMM's epilogue tiles
+        fuse = lens is None and Ts % 128 == 0 and C % 128 == 0
         cs, acts, per_block = [c], [a], []
         for convs, gn_at, skip in blocks:
             src, hs, mrs, gs, gkw = acts[-1], [], [], [], {}
@@ -637,12 +687,18 @@ def _encoder_rows(plan, inp, B, T, ts, ragged=False):
                         gkw = dict(gn_tiles=gst)  # merged inside the skip GEMM
                     else:
                         ops.gn_finalize_tiles(gst, N, Ts, C, 1, mr)
+                elif lens is not None:
+                    _fwd(cv, src, w, h, Ts, bias=ts[cv.at + 1])
+                    ops.groupnorm_stats_len(h, Ts, 1, lens, gn_part, mr)
                 else:
                     _fwd(cv, src, w, h, Ts, bias=ts[cv.at + 1])
                     ops.groupnorm_stats(h, Ts, 1, gn_part, mr)
                 if not last:  # LeakyReLU(GN(h)): the next conv's operand (layers.py:156-161)
                     g = e(N, C, dtype=dt)
-                    ops.gn_lrelu_fwd(h, g, Ts, mr, ts[ag], ts[ag + 1])
+                    if lens is not None:
+                        ops.gn_lrelu_fwd_len(h, g, Ts, lens, mr, ts[ag], ts[ag + 1])
+                    else:
+                        ops.gn_lrelu_fwd(h, g, Ts, mr, ts[ag], ts[ag + 1])
                     gs.append(g)
                     src = g
                 hs.append(h)
@@ -651,6 +707,10 @@ def _encoder_rows(plan, inp, B, T, ts, ragged=False):
             c, a = e(N, C, dtype=dt), e(N, C, dtype=dt)
             _fwd(skip, cs[-1], w, c, Ts, bias=ts[skip.at + 1], gn_h=hs[-1], gn_mr=mrs[-1], gn_gamma=ts[gn_at[-1]],
                  gn_beta=ts[gn_at[-1] + 1], act=L.PRO_LRELU, y2=a, **gkw)
+            if lens is not None:
+                ops.mask_tail(a, Ts, lens)
+                if skip.k > 1:
+                    ops.mask_tail(c, Ts, lens)
             cs.append(c)
             acts.append(a)
             per_block.append((hs, mrs, gs))
@@ -804,18 +864,33 @@ class Encoder(_Encoder):
         save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, *ts) if t is not None)
         return _EncoderFn.apply(plan, save, x, *ts)
 
-    def forward_rows(self, x_rows, B, T):
+    def forward_rows(self, x_rows, B, T, lengths=None):
         """forward without gradients on the frame-major input x_rows [B*T, C_in]
         in the compute dtype: (z f32 [B*T', z_channels] rows, feat [B*T', C]
         rows in the compute dtype, T').  One utterance (B == 1) may have any
         length that leaves every stage a frame (_encoder_rows states the
-        ragged stages); forward itself keeps refusing such a T."""
+        ragged stages); forward itself keeps refusing such a T.  lengths: host
+        ints, utterance b owns rows t < lengths[b] of a padded T that is a
+        multiple of the down-sampling; x_rows holds zeros elsewhere
+        (_encoder_rows)."""
         if self._plan is None:
             self._plan = _EncPlan(self)
         plan = self._plan
         if not x_rows.is_cuda or x_rows.dim() != 2 or x_rows.dtype != plan.dt or x_rows.stride(1) != 1 \
                 or tuple(x_rows.shape) != (B * T, self.in_ch):
             raise ValueError(f"vqvae2.Encoder: x_rows must be device [{B * T}, {self.in_ch}] rows in {plan.dt}")
+        if lengths is not None:
+            lens = list(ops.len_array(lengths, B, "vqvae2.Encoder lengths"))
+            if any(not 1 <= n <= T for n in lens):
+                raise ValueError(f"vqvae2.Encoder: lengths must lie in 1..T = {T}")
+            for conv, _ in plan.stages:
+                lens = [_stage_frames(n, conv.scale) for n in lens]
+                if min(lens) < 1:
+                    raise ValueError(f"vqvae2.Encoder: an utterance of {lengths[lens.index(min(lens))]} frames leaves a "
+                                     "stage without a frame")
+            with torch.no_grad():
+                ts = [None if t is None else t.detach().float() for t in _EncPlan.tensors(self, plan)]
+                return _encoder_rows(plan, x_rows, B, T, ts, lengths=lengths)[:3]
         ragged, T_in = False, T
         for conv, _ in plan.stages:
             ragged |= T_in % conv.scale != 0
@@ -873,7 +948,8 @@ class Model(nn.Module):
     Conversion: analyze(x) -> the codes forward picks, synthesize((codes, y))
     -> xhat from codes, convert((x, y)) = the two together = the xhat of
     forward((x, y)).  All three run without gradients and write no parameter
-    or buffer; one utterance at a time may have any length.
+    or buffer; one utterance at a time may have any length, and so may the
+    utterances of a padded batch given with its `lengths`.
 
     Not built (NotImplementedError): use_ema: true (EMAVectorQuantizer.forward
     inside the hierarchy), jitter_p != 0, and encode / decode / infer, whose
@@ -970,7 +1046,77 @@ class Model(nn.Module):
     def _is_style(self, i):
         return self.use_gst and i == self.levels - 1
 
-    def analyze(self, x):
+    def level_lengths(self, lengths):
+        """Host arithmetic: [[frames of utterance b at level i] for every level i]
+        for utterances of `lengths` input frames (level 0 first; the strided
+        stage convs floor, _stage_frames).  ValueError when an utterance
+        leaves a level without a frame."""
+        lengths = lens = list(ops.len_array(lengths, what="vqvae2.Model lengths"))
+        out = []
+        for i, enc in enumerate(self.encoders):
+            for k in enc.stage_index:
+                lens = [_stage_frames(n, getattr(enc.encode[k], "scale", 1)) for n in lens]
+            if min(lens) < 1:
+                b = lens.index(min(lens))
+                raise ValueError(f"vqvae2.Model: utterance {b} of {lengths[b]} frames leaves level {i} without a frame")
+            out.append(lens)
+        return out
+
+    def _batch_lengths(self, lengths, B, who):
+        """(lengths as a list, level_lengths, the padded level-0 frame count's granule)."""
+        lens = list(ops.len_array(lengths, B, f"{who} lengths"))
+        return lens, self.level_lengths(lens), math.prod(_total_scale(enc) for enc in self.encoders)
+
+    def _analyze_lengths(self, x, lengths):
+        """analyze for a padded batch: utterance b owns frames t < lengths[b]."""
+        who = "vqvae2.Model.analyze"
+        B, mel, T = x.shape
+        lens, lv, gran = self._batch_lengths(lengths, B, who)
+        if max(lens) > T:
+            raise ValueError(f"{who}: lengths up to {max(lens)} exceed x's {T} frames")
+        with torch.no_grad():
+            dt, dev = _DT[self.compute_dtype], x.device
+            e = functools.partial(torch.empty, device=dev)
+            Tp = -(-T // gran) * gran  # every level's padded length divides exactly
+            x = x.float()
+            if Tp != T:
+                xp = x.new_zeros(B, mel, Tp)
+                xp[:, :, :T] = x
+                x = xp
+            feat = ops.nct_to_ntc(x.contiguous(), e(B * Tp, mel, dtype=dt))
+            ops.mask_tail(feat, Tp, lens)  # the input's padding is never trusted
+            Ti, zs, lin = Tp, [], lens
+            for i, enc in enumerate(self.encoders):
+                z, feat, Ti = enc.forward_rows(feat, B, Ti, lengths=lin)
+                zs.append((z, Ti))
+                lin = lv[i]
+            codes, cond, cond_len = [None] * self.levels, [], []  # cond: the levels of codes_upsample_cat_len, top first
+            z, Ti = zs.pop()
+            for i in reversed(range(self.levels)):
+                q = self.quantizers[i]
+                if self._is_style(i):
+                    mean = ops.segment_mean(z, Ti, lv[i], e(B, z.shape[1], dtype=F32))
+                    style = q.pool_rows(mean, 1)
+                    codes[i] = style.unsqueeze(-1)
+                    cond.append(style)
+                    cond_len.append([1] * B)
+                else:
+                    idx = q.encode(z.view(B, Ti, -1), time_last=False)  # tail entries: whatever the pad rows gave
+                    Tm = max(lv[i])
+                    keep = (torch.arange(Tm)[None, :] < torch.tensor(lv[i])[:, None]).to(dev)
+                    codes[i] = torch.where(keep, idx[:, :Tm], torch.zeros((), dtype=idx.dtype, device=dev))
+                    cond.append((idx, q.embeddings.detach(), q.normalize))
+                    cond_len.append(lv[i])
+                if i > 0:
+                    z, Ti = zs.pop()
+                    ops.mask_tail(z, Ti, lv[i - 1])  # the encoder's z becomes a decoder's input
+                    xin = z if dt == F32 else ops.convert_2d(z, e(z.shape, dtype=dt))
+                    dec = self.decoders[i]
+                    full = ops.codes_upsample_cat_len(cond, B, Ti, lv[i - 1], cond_len, e(B * Ti, dec.cond_ch, dtype=F32))
+                    z = dec.forward_rows(xin, B, Ti, [full], lengths=lv[i - 1])
+            return codes
+
+    def analyze(self, x, lengths=None):
         """x (B, mel, T) -> the codes forward would pick, one entry per level in
         level order: int64 indices (B, T_i) of a quantized level, the style
         embedding (B, F, 1) f32 of a style-token top level.  Computed in
@@ -978,11 +1124,24 @@ class Model(nn.Module):
         lower levels' quantizer inputs) on frame-major rows throughout, under
         no_grad; no parameter or buffer is written (forward renormalises the
         codebooks in place; here they are normalised on the fly).  One utterance
-        (B == 1) may have any length that leaves every level a frame."""
+        (B == 1) may have any length that leaves every level a frame.
+
+        lengths (a host sequence or a CPU int tensor, never a device tensor):
+        a padded batch, utterance b owning frames t < lengths[b] <= T; whatever
+        x holds from lengths[b] on is ignored.  A quantized level comes back
+        as int64 (B, max_b len_i[b]) with 0 at the padded positions
+        (level_lengths gives len_i), the style level as (B, F, 1).  Each
+        utterance gets the codes it would get alone."""
         if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != self.encoders[0].in_ch:
             raise ValueError(f"vqvae2.Model.analyze: x must be (B, {self.encoders[0].in_ch}, T)")
+        if lengths is not None:  # validated on the host before the device is touched
+            lens, _, _ = self._batch_lengths(lengths, x.shape[0], "vqvae2.Model.analyze")
+            if max(lens) > x.shape[2]:
+                raise ValueError(f"vqvae2.Model.analyze: lengths up to {max(lens)} exceed x's {x.shape[2]} frames")
         if not x.is_cuda:
             raise L.VqxError("vqvae2.Model runs on the MI355X only (libvqx); move it and its inputs with .cuda()")
+        if lengths is not None:
+            return self._analyze_lengths(x, lengths)
         with torch.no_grad():
             B, _, T = x.shape
             dt = _DT[self.compute_dtype]
@@ -1057,7 +1216,46 @@ class Model(nn.Module):
                                      f"holds 0..{K - 1}")
         return codes, B, T
 
-    def synthesize(self, input, time=None):
+    def _synthesize_lengths(self, codes, y_idx, time, lengths):
+        """synthesize for a padded batch: utterance b has lengths[b] output frames."""
+        who = "vqvae2.Model.synthesize"
+        if not torch.is_tensor(y_idx) or y_idx.dim() != 2:
+            raise ValueError(f"{who}: y_idx must be (B, 1) speaker indices")
+        lens, lv, _ = self._batch_lengths(lengths, y_idx.shape[0], who)
+        if time is not None and int(time) != max(lens):
+            raise ValueError(f"{who}: with lengths the output has max(lengths) = {max(lens)} frames; time = {time}")
+        codes = list(codes)
+        for i, c in enumerate(codes[:self.levels]):
+            if not torch.is_tensor(c):
+                continue  # _check_codes names it
+            if self._is_style(i):
+                if c.dim() == 3 and c.shape[2] != 1:
+                    raise ValueError(f"{who}: with lengths the style level is (B, F, 1), got {tuple(c.shape)}")
+            elif c.dim() == 2 and c.shape[1] < max(lv[i]):
+                raise ValueError(f"{who}: level {i} holds {c.shape[1]} frames, the lengths need {max(lv[i])}")
+        codes, B, T = self._check_codes(codes, y_idx, max(lens))
+        if not all(c.is_cuda for c in codes) or not y_idx.is_cuda:
+            raise L.VqxError("vqvae2.Model runs on the MI355X only (libvqx); move it and its inputs with .cuda()")
+        with torch.no_grad():
+            levels, level_len = [], []
+            for i in reversed(range(self.levels)):
+                c, q = codes[i], self.quantizers[i]
+                if self._is_style(i):
+                    levels.append(c.float().reshape(B, -1))
+                    level_len.append([1] * B)
+                else:
+                    c = c.contiguous()
+                    if c.data_ptr() % 16:  # a slice of a longer index tensor: the kernel reads aligned pointers
+                        c = c.clone()
+                    levels.append((c, q.embeddings.detach(), q.normalize))
+                    level_len.append(lv[i])
+            dec = self.decoders[0]
+            rows = torch.empty(B * T, dec.layers[0].cin, device=y_idx.device, dtype=_DT[self.compute_dtype])
+            ops.codes_upsample_cat_len(levels, B, T, lens, level_len, rows)
+            y = self.embeds(y_idx[..., :1]).reshape(B, -1)
+            return _to_nct(dec.forward_rows(rows, B, T, [y], lengths=lens), B, T)
+
+    def synthesize(self, input, time=None, lengths=None):
         """((codes, y_idx (B, 1)), time) -> xhat (B, mel, T): decoders[0] on the
         codes of `analyze` (entries may come from different calls, e.g. the style
         of another utterance) with the speaker embedding as conditioning, as
@@ -1065,8 +1263,15 @@ class Model(nn.Module):
         frame-major input from the indices, channels stacked top level first.
         T = `time`, else codes[0]'s frames times encoder 0's down-sampling.
         Under no_grad; writes no parameter or buffer.  Bad codes raise
-        ValueError before any libvqx launch."""
+        ValueError before any libvqx launch.
+
+        lengths (host values, as analyze): the codes of a padded batch as
+        analyze(x, lengths) returns them; xhat is (B, mel, max(lengths)) with
+        zeros at t >= lengths[b], each utterance rendered as it would be alone
+        (its own stretch factors, GroupNorm statistics and conv padding)."""
         codes, y_idx = input
+        if lengths is not None:
+            return self._synthesize_lengths(codes, y_idx, time, lengths)
         codes, B, T = self._check_codes(codes, y_idx, time)
         if not all(c.is_cuda for c in codes) or not y_idx.is_cuda:
             raise L.VqxError("vqvae2.Model runs on the MI355X only (libvqx); move it and its inputs with .cuda()")
@@ -1087,10 +1292,13 @@ class Model(nn.Module):
             y = self.embeds(y_idx[..., :1]).reshape(B, -1)
             return _to_nct(dec.forward_rows(rows, B, T, [y]), B, T)
 
-    def convert(self, input):
+    def convert(self, input, lengths=None):
         """(x (B, mel, T), y_idx (B, 1)) -> x rendered with speaker y_idx:
-        synthesize((analyze(x), y_idx), time=T), the xhat of forward((x, y_idx))."""
+        synthesize((analyze(x), y_idx), time=T), the xhat of forward((x, y_idx)).
+        lengths: a padded batch (analyze, synthesize); (B, mel, max(lengths))."""
         x, y_idx = input
+        if lengths is not None:
+            return self.synthesize((self.analyze(x, lengths), y_idx), lengths=lengths)
         return self.synthesize((self.analyze(x), y_idx), time=x.shape[2])
 
     def encode(self, input):

@@ -1158,6 +1158,35 @@ def upsample_cat_bwd_to(dlevels, B, T, dout):
     return dlevels
 
 
+def _codes_levels(levels, B, what):
+    """vqx_codes_level array of dense levels / (idx, codebook, normalize) tuples; returns (array, sum of C_l)."""
+    if not 1 <= len(levels) <= HIER_MAX_LEVELS:
+        raise ValueError(f"{what}: {len(levels)} levels, 1..{HIER_MAX_LEVELS} are supported")
+    arr, total = (L.CodesLevel * len(levels))(), 0
+    for e, lv in zip(arr, levels):
+        if torch.is_tensor(lv):
+            z = lv
+            _check_cuda(z)
+            if z.dtype != torch.float32 or z.dim() != 2 or z.stride(1) != 1 or z.shape[0] % B:
+                raise ValueError(f"{what}: a dense level must be f32 [B*T_l, C_l] rows with unit column "
+                                 "stride")
+            e.z, e.idx, e.T_l, e.C, e.ld = ptr(z), None, z.shape[0] // B, z.shape[1], z.stride(0)
+            _rows(z, z.shape[0], e.ld, e.C, f"{what} level")
+        else:
+            idx, E, normalize = lv
+            _check_cuda(idx, E)
+            if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != B or not idx.is_contiguous():
+                raise ValueError(f"{what}: indices must be a contiguous int64 ({B}, T_l) tensor")
+            if E.dtype != torch.float32 or E.dim() != 2 or E.stride(1) != 1:
+                raise ValueError(f"{what}: a codebook must be f32 [K, D] rows with unit column stride")
+            e.z, e.idx, e.T_l, e.C, e.ld = ptr(E), ptr(idx), idx.shape[1], E.shape[1], E.stride(0)
+            e.K, e.normalize = E.shape[0], int(bool(normalize))
+            _span(idx, idx.numel(), f"{what} idx")
+            _rows(E, e.K, e.ld, e.C, f"{what} codebook")
+        total += e.C
+    return arr, total
+
+
 def codes_upsample_cat(levels, B, T, out):
     """The first decoder's frame-major input from codes in one launch
     (vqx_codes_upsample_cat).  A level is a dense f32 tensor [B*T_l, C_l] (as in
@@ -1165,35 +1194,124 @@ def codes_upsample_cat(levels, B, T, out):
     normalize): out[b*T + t, off_l + c] = codebook[idx[b, src_l(t)], c], divided
     by the row's L2 norm with `normalize`.  out f32 or bf16 [B*T, >= sum C_l].
     The indices are not checked here (the caller's job, Model.synthesize)."""
-    if not 1 <= len(levels) <= HIER_MAX_LEVELS:
-        raise ValueError(f"codes_upsample_cat: {len(levels)} levels, 1..{HIER_MAX_LEVELS} are supported")
-    arr, total = (L.CodesLevel * len(levels))(), 0
-    for e, lv in zip(arr, levels):
-        if torch.is_tensor(lv):
-            z = lv
-            _check_cuda(z)
-            if z.dtype != torch.float32 or z.dim() != 2 or z.stride(1) != 1 or z.shape[0] % B:
-                raise ValueError("codes_upsample_cat: a dense level must be f32 [B*T_l, C_l] rows with unit column "
-                                 "stride")
-            e.z, e.idx, e.T_l, e.C, e.ld = ptr(z), None, z.shape[0] // B, z.shape[1], z.stride(0)
-            _rows(z, z.shape[0], e.ld, e.C, "codes_upsample_cat level")
-        else:
-            idx, E, normalize = lv
-            _check_cuda(idx, E)
-            if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != B or not idx.is_contiguous():
-                raise ValueError(f"codes_upsample_cat: indices must be a contiguous int64 ({B}, T_l) tensor")
-            if E.dtype != torch.float32 or E.dim() != 2 or E.stride(1) != 1:
-                raise ValueError("codes_upsample_cat: a codebook must be f32 [K, D] rows with unit column stride")
-            e.z, e.idx, e.T_l, e.C, e.ld = ptr(E), ptr(idx), idx.shape[1], E.shape[1], E.stride(0)
-            e.K, e.normalize = E.shape[0], int(bool(normalize))
-            _span(idx, idx.numel(), "codes_upsample_cat idx")
-            _rows(E, e.K, e.ld, e.C, "codes_upsample_cat codebook")
-        total += e.C
+    arr, total = _codes_levels(levels, B, "codes_upsample_cat")
     _check_cuda(out)
     if out.dim() != 2 or out.shape[0] != B * T or out.stride(1) != 1:
         raise ValueError(f"codes_upsample_cat: out must be [{B * T}, C] rows with unit column stride")
     _rows(out, out.shape[0], out.stride(0), total, "codes_upsample_cat out")
     call("vqx_codes_upsample_cat", arr, len(levels), B, T, ptr(out), out.stride(0), dt_code(out.dtype), stream_ptr())
+    return out
+
+
+# ---- a batch of different lengths (vqx_varlen.hip): `lengths` are host values
+def len_array(lengths, B=None, what="lengths"):
+    """Per-utterance lengths as the host int32 array the *_len entry points take:
+    a sequence of ints or a CPU integer tensor (a device tensor is refused: it
+    would cost a read-back), or an array this function returned, passed through."""
+    if isinstance(lengths, ctypes.Array):
+        arr = lengths
+    else:
+        if torch.is_tensor(lengths):
+            if lengths.is_cuda or lengths.is_floating_point() or lengths.dim() != 1:
+                raise ValueError(f"{what} must be host values: a sequence of ints or a 1-D CPU integer tensor, never a "
+                                 "device tensor")
+            lengths = lengths.tolist()
+        vals = list(lengths)
+        if not vals or any(isinstance(v, bool) or not isinstance(v, int) for v in vals):
+            raise ValueError(f"{what} must be a non-empty sequence of ints")
+        if any(not -2 ** 31 <= v < 2 ** 31 for v in vals):
+            raise ValueError(f"{what} must fit 32 bits")
+        arr = (ctypes.c_int32 * len(vals))(*vals)
+    if B is not None and len(arr) != B:
+        raise ValueError(f"{what}: {len(arr)} entries for a batch of {B}")
+    return arr
+
+
+def _len_rows(t, T, lengths, what):
+    """Checks shared by the *_len ops on rows t [B*T, C]: returns the host array of B lengths."""
+    _check_cuda(t)
+    if t.dim() != 2 or t.stride(1) != 1 or T < 1 or t.shape[0] % T or t.shape[0] < T:
+        raise ValueError(f"{what}: rows must be [B*T, C] with unit column stride, T = {T}")
+    return len_array(lengths, t.shape[0] // T, f"{what} lengths")
+
+
+def groupnorm_stats_len(x, T, G, lengths, partials, mean_rstd, eps=1e-5):
+    """groupnorm_stats over rows t < lengths[b] of every utterance (vqx_groupnorm_stats_len)."""
+    arr = _len_rows(x, T, lengths, "groupnorm_stats_len")
+    B = len(arr)
+    _check_cuda(partials, mean_rstd)
+    if partials.numel() < B * G * 24 or mean_rstd.numel() < B * G * 2 or partials.dtype != torch.float32 \
+            or mean_rstd.dtype != torch.float32:
+        raise ValueError(f"groupnorm_stats_len: partials needs {B * G * 24} floats, mean_rstd {B * G * 2}")
+    _rows(x, x.shape[0], x.stride(0), x.shape[1], "groupnorm_stats_len x")
+    call("vqx_groupnorm_stats_len", ptr(x), x.stride(0), dt_code(x.dtype), x.shape[0], T, x.shape[1], G, arr, eps,
+         ptr(partials), ptr(mean_rstd), stream_ptr())
+    return mean_rstd
+
+
+def _gn_len_apply(name, h, g, T, cols, lengths, mean_rstd, gamma, beta, G):
+    arr = _len_rows(h, T, lengths, name)
+    _check_cuda(g, mean_rstd, gamma, beta)
+    if g.dim() != 2 or g.shape[0] != h.shape[0] or g.shape[1] < cols or g.stride(1) != 1 or g.dtype != h.dtype:
+        raise ValueError(f"{name}: the output must be [{h.shape[0]}, >= {cols}] rows of the input's dtype")
+    if any(t.dtype != torch.float32 for t in (mean_rstd, gamma, beta)) or mean_rstd.numel() < len(arr) * G * 2 \
+            or gamma.numel() < h.shape[1] or beta.numel() < h.shape[1]:
+        raise ValueError(f"{name}: mean_rstd [B, {G}, 2], gamma and beta [C] must be f32")
+    _rows(h, h.shape[0], h.stride(0), h.shape[1], f"{name} in")
+    _rows(g, g.shape[0], g.stride(0), cols, f"{name} out")
+    call("vqx_" + name, ptr(h), h.stride(0), ptr(g), g.stride(0), dt_code(h.dtype), h.shape[0], T, h.shape[1], arr,
+         ptr(mean_rstd), ptr(gamma), ptr(beta), stream_ptr())
+    return g
+
+
+def gn_lrelu_fwd_len(h, g, T, lengths, mean_rstd, gamma, beta):
+    """gn_lrelu_fwd on rows t < lengths[b]; rows from lengths[b] up are written as zeros (vqx_gn_lrelu_fwd_len)."""
+    return _gn_len_apply("gn_lrelu_fwd_len", h, g, T, h.shape[1], lengths, mean_rstd, gamma, beta, 1)
+
+
+def gn_glu_fwd_len(u, g, T, lengths, mean_rstd, gamma, beta):
+    """gn_glu_fwd on rows t < lengths[b]; rows from lengths[b] up are written as zeros (vqx_gn_glu_fwd_len)."""
+    return _gn_len_apply("gn_glu_fwd_len", u, g, T, u.shape[1] // 2, lengths, mean_rstd, gamma, beta, 2)
+
+
+def mask_tail(x, T, lengths):
+    """x[b*T + t, :] = 0 for lengths[b] <= t < T, in place (vqx_mask_tail)."""
+    arr = _len_rows(x, T, lengths, "mask_tail")
+    _rows(x, x.shape[0], x.stride(0), x.shape[1], "mask_tail x")
+    call("vqx_mask_tail", ptr(x), x.stride(0), dt_code(x.dtype), x.shape[0], T, x.shape[1], arr, stream_ptr())
+    return x
+
+
+def codes_upsample_cat_len(levels, B, T, lengths, level_lengths, out):
+    """codes_upsample_cat for a padded batch (vqx_codes_upsample_cat_len): utterance
+    b has lengths[b] <= T output frames and level_lengths[l][b] frames at level
+    l (stored with the level's own padded T_l); its rows from lengths[b] up are
+    zeros.  Levels as in codes_upsample_cat."""
+    arr, total = _codes_levels(levels, B, "codes_upsample_cat_len")
+    n_arr = len_array(lengths, B, "codes_upsample_cat_len lengths")
+    if len(level_lengths) != len(levels):
+        raise ValueError(f"codes_upsample_cat_len: {len(level_lengths)} length lists for {len(levels)} levels")
+    per_level = [len_array(m, B, f"codes_upsample_cat_len level {l} lengths") for l, m in enumerate(level_lengths)]
+    m_arr = (ctypes.c_int32 * (B * len(levels)))(*[per_level[l][b] for b in range(B) for l in range(len(levels))])
+    _check_cuda(out)
+    if out.dim() != 2 or out.shape[0] != B * T or out.stride(1) != 1:
+        raise ValueError(f"codes_upsample_cat_len: out must be [{B * T}, C] rows with unit column stride")
+    _rows(out, out.shape[0], out.stride(0), total, "codes_upsample_cat_len out")
+    call("vqx_codes_upsample_cat_len", arr, len(levels), B, T, n_arr, m_arr, ptr(out), out.stride(0),
+         dt_code(out.dtype), stream_ptr())
+    return out
+
+
+def segment_mean(z, T, lengths, out):
+    """out[b, c] = mean over t < lengths[b] of z[b*T + t, c], f32 (vqx_segment_mean)."""
+    arr = _len_rows(z, T, lengths, "segment_mean")
+    _check_cuda(out)
+    if z.dtype != torch.float32 or out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 \
+            or tuple(out.shape) != (len(arr), z.shape[1]):
+        raise ValueError(f"segment_mean: z must be f32 rows and out f32 [{len(arr)}, {z.shape[1]}]")
+    _rows(z, z.shape[0], z.stride(0), z.shape[1], "segment_mean z")
+    call("vqx_segment_mean", ptr(z), z.stride(0), z.shape[0], T, z.shape[1], arr, ptr(out), out.stride(0),
+         stream_ptr())
     return out
 
 
