@@ -7,7 +7,7 @@
     torch restatement of its blocks, bound as tests/test_gpu_hier.py bounds the
     conditioned one (max|got - f64| / max|f64| <= max(8 * err32, 16 * 2^-23)
     per tensor, err32 the restatement's own float32 error), and a conditioned
-    one through `_DecoderFn` bit-equal to `_decoder_rows` + `_decoder_rows_bwd`
+    one through `_DecoderFn` bit-equal to `decoder_rows` + `decoder_rows_bwd`
     called on rows;
   * the fused decode side (`vqvae2b.decode_side`) bit-identical to the same
     decoders composed from `Decoder` modules and `upsample_cat`: the launches
@@ -190,10 +190,11 @@ def test_unconditioned_decoder_matches_the_float64_restatement(T):
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_conditioned_decoder_equals_the_rows_functions_bit_for_bit(dtype):
-    """`_DecoderFn` (through Decoder.forward) against `_decoder_rows` + `_decoder_rows_bwd` called directly with the
+    """`_DecoderFn` (through Decoder.forward) against `decoder_rows` + `decoder_rows_bwd` called directly with the
     same layout changes around them: the split moved no launch."""
     from vae_npvc_amd import ops
-    from vae_npvc_amd.model import vqvae2 as V
+    from vae_npvc_amd.model.hier_common import DT, to_nct, to_rows
+    from vae_npvc_amd.model.hier_decoder import Plan, decoder_rows, decoder_rows_bwd
     B, T, lens = 2, 37, (1, 9)
     dec = seeded_decoder(dict(DEC_ARGS, cond_channels=24), 9850, dtype).cuda()
     g = torch.Generator().manual_seed(5)
@@ -202,23 +203,22 @@ def test_conditioned_decoder_equals_the_rows_functions_bit_for_bit(dtype):
     go = torch.randn(B, 24, T, generator=g).cuda()
     out = dec((x, levels))
     out.backward(go)
-    plan, dt = dec._plan, V._DT[dtype]
+    plan, dt = dec.plan, DT[dtype]
     with torch.no_grad():
-        ts = [t.detach().float() for t in V._Plan.tensors(dec)]
+        ts = [t.detach().float() for t in Plan.tensors(dec)]
         x2 = ops.nct_to_ntc(x.detach().contiguous(), torch.empty(B * T, 32, device=DEV, dtype=dt))
-        rows = [V._to_rows(z.detach()) for z in levels]
-        xhat, (Tc, c_low, saved, wp, a_skip, f1, w1, w2) = V._decoder_rows(plan, x2, B, T, rows, lens, ts)
-        wp[plan.fin1.at], wp[plan.fin2.at] = w1, w2
+        rows = [to_rows(z.detach()) for z in levels]
+        xhat, keep = decoder_rows(plan, x2, B, T, rows, lens, ts)
         dxhat = ops.nct_to_ntc(go, torch.empty(B * T, 24, device=DEV, dtype=dt))
-        dx, dc, grads = V._decoder_rows_bwd(plan, B, T, Tc, (saved, wp, a_skip, f1, c_low, ts), dxhat)
+        dx, dc, grads = decoder_rows_bwd(plan, B, T, keep, dxhat)
         dl = [torch.empty(B * Tl, z.shape[1], device=DEV) for z, Tl in zip(levels, lens)]
-        ops.upsample_cat_bwd(dl, B, Tc, dc)
-    assert torch.equal(V._to_nct(xhat, B, T), out.detach())
-    assert torch.equal(V._to_nct(dx, B, T), x.grad)
+        ops.upsample_cat_bwd(dl, B, keep.Tc, dc)
+    assert torch.equal(to_nct(xhat, B, T), out.detach())
+    assert torch.equal(to_nct(dx, B, T), x.grad)
     for d, z in zip(dl, levels):
-        assert torch.equal(V._to_nct(d, B, z.shape[2]), z.grad)
+        assert torch.equal(to_nct(d, B, z.shape[2]), z.grad)
     # dL/d(effective weight) through torch's weight norm, as autograd applies it to the function's outputs
-    live = [(t, gr) for t, gr in zip(V._Plan.tensors(dec), grads) if t.requires_grad]
+    live = [(t, gr) for t, gr in zip(Plan.tensors(dec), grads) if t.requires_grad]
     params = list(dec.parameters())
     want = [p.grad.clone() for p in params]
     dec.zero_grad(set_to_none=True)

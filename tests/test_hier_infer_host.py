@@ -110,7 +110,7 @@ def test_ops_wrapper_refuses_host_tensors_and_bad_levels():
 # ------------------------------------------------------------------ model
 def test_stage_frames_are_the_strided_convs_output_lengths():
     """kernel 2s, stride s, padding s//2 + s%2 against torch's conv on the CPU, ragged lengths included."""
-    from vae_npvc_amd.model.vqvae2 import _stage_frames
+    from vae_npvc_amd.model.hier_encoder import stage_frames as _stage_frames
     for s in (2, 3, 4, 5):
         conv = torch.nn.Conv1d(1, 1, 2 * s, stride=s, padding=s // 2 + s % 2)
         for T in range(s, 4 * s + 2):

@@ -89,7 +89,7 @@ def test_unconditioned_resskip_block_owns_no_conv_cond():
 
 
 def test_decoder_plan_indexes_six_tensors_per_unconditioned_block():
-    from vae_npvc_amd.model.vqvae2 import Decoder, _Plan
+    from vae_npvc_amd.model.hier_decoder import Decoder, Plan as _Plan
     args = fixture("vq2b", "ema_gst")[0]["arch"]["final_decoder"]
     free, cond = Decoder(**args), Decoder(**dict(args, cond_channels=16))
     blocks = sum(args["stacks"])

@@ -28,13 +28,13 @@ from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
 from .. import ops
+from .hier_base import HierModelBase
+from .hier_common import DT, F32, mean_pool, src_index, to_nct, to_rows
+from .hier_decoder import Decoder, Plan, decoder_rows, decoder_rows_bwd
+from .hier_encoder import Encoder
 from .layers import Conditions
 from .layers_gst import StyleTokenLayer
 from .layers_vq import EMAVectorQuantizer, Jitter, VectorQuantizer
-from .vqvae2 import (_DT, F32, Decoder, Encoder, _decoder_rows, _decoder_rows_bwd, _LogLossFn, _Plan, _to_nct,
-                     _to_rows, src_index)
-from .vqvae2 import Model as _Vqvae2Model
-from .vqvae2a import mean_pool
 
 
 class _DecodeSideFn(torch.autograd.Function):
@@ -59,28 +59,25 @@ class _DecodeSideFn(torch.autograd.Function):
             at += p.n_tensors
         outs, keeps, dims = [], [], []
         for i in range(nl):
-            plan, z = plans[i], zs[i]
+            z = zs[i]
             C, Ti = z.shape[1], z.shape[2]
             Td = Ti if upsample_last else time
             if Td == Ti:  # the level at the decoder's own rate: the one layout change, into the compute dtype
                 x2 = ops.nct_to_ntc(z.float().contiguous(), e(B * Ti, C, dtype=dt))
             else:
-                x2 = ops.upsample_cat_fwd([_to_rows(z)], B, Td, e(B * Td, C, dtype=dt))
+                x2 = ops.upsample_cat_fwd([to_rows(z)], B, Td, e(B * Td, C, dtype=dt))
             y = ys[i].detach().float().contiguous()
-            xh, (Tc, c_low, saved, wp, a_skip, f1, w1, w2) = _decoder_rows(plan, x2, B, Td, [y], (1,), ts[i])
-            wp[plan.fin1.at], wp[plan.fin2.at] = w1, w2
+            xh, keep = decoder_rows(plans[i], x2, B, Td, [y], (1,), ts[i])
             outs.append(xh)
-            keeps.append((saved, wp, a_skip, f1, c_low, ts[i]) if save else None)
-            dims.append((Ti, Td, Tc, C))
+            keeps.append(keep if save else None)
+            dims.append((Ti, Td, C))
         # the join: stretch the shorter levels, stack on channels, round once to the compute dtype
-        fin = plans[nl]
         joined = ops.upsample_cat_fwd(outs, B, time, e(B * time, sum(o.shape[1] for o in outs), dtype=dt))
-        xhat, (_, _, saved, wp, a_skip, f1, w1, w2) = _decoder_rows(fin, joined, B, time, None, (), ts[nl])
+        xhat, keep = decoder_rows(plans[nl], joined, B, time, None, (), ts[nl])
         if save:
-            wp[fin.fin1.at], wp[fin.fin2.at] = w1, w2
-            keeps.append((saved, wp, a_skip, f1, None, ts[nl]))
+            keeps.append(keep)
             ctx.cfg, ctx.B, ctx.dims, ctx.keeps = cfg, B, dims, keeps
-        return _to_nct(xhat, B, time)
+        return to_nct(xhat, B, time)
 
     @staticmethod
     @once_differentiable
@@ -92,23 +89,23 @@ class _DecodeSideFn(torch.autograd.Function):
         fin, dt = plans[nl], plans[nl].dt
         e = functools.partial(torch.empty, device=dout.device)
         dxhat = ops.nct_to_ntc(dout.float().contiguous(), e(B * time, fin.final, dtype=dt))
-        dx, _, g_fin = _decoder_rows_bwd(fin, B, time, None, keeps[nl], dxhat)
+        dx, _, g_fin = decoder_rows_bwd(fin, B, time, keeps[nl], dxhat)
         # every level decoder's output gradient: the fp32 sums over its segments, stored in the compute dtype
-        dl = [e(B * Td, plans[i].final, dtype=dt) for i, (_, Td, _, _) in enumerate(dims)]
+        dl = [e(B * Td, plans[i].final, dtype=dt) for i, (_, Td, _) in enumerate(dims)]
         ops.upsample_cat_bwd_to(dl, B, time, dx)
         dzs, dys, grads = [], [], []
         for i in range(nl):
-            Ti, Td, Tc, C = dims[i]
-            dxi, dc, g = _decoder_rows_bwd(plans[i], B, Td, Tc, keeps[i], dl[i])
+            Ti, Td, C = dims[i]
+            dxi, dc, g = decoder_rows_bwd(plans[i], B, Td, keeps[i], dl[i])
             grads += g
             dys.append(dc if ctx.needs_input_grad[2 + nl + i] else None)  # Tc == 1: dc is the speaker rows' gradient
             if not ctx.needs_input_grad[2 + i]:
                 dzs.append(None)
             elif Td == Ti:
-                dzs.append(_to_nct(dxi, B, Ti))
+                dzs.append(to_nct(dxi, B, Ti))
             else:
                 dz = ops.upsample_cat_bwd([e(B * Ti, C, dtype=F32)], B, Td, dxi)[0]
-                dzs.append(_to_nct(dz, B, Ti))
+                dzs.append(to_nct(dz, B, Ti))
         return (None, None, *dzs, *dys, *grads, *g_fin)
 
 
@@ -134,16 +131,14 @@ def decode_side(decoders, final_decoder, z_vqs, ys, time, upsample_last):
     mods = [*decoders, final_decoder]
     if len({d.compute_dtype for d in mods}) != 1:
         raise ValueError("decode_side: the decoders must share one compute_dtype")
-    for d in mods:
-        if d._plan is None:
-            d._plan = _Plan(d)
-    flat = [t for d in mods for t in _Plan.tensors(d)]
+    plans = tuple(d.plan for d in mods)
+    flat = [t for d in mods for t in Plan.tensors(d)]
     save = torch.is_grad_enabled() and any(t.requires_grad for t in (*z_vqs, *ys, *flat))
-    cfg = (tuple(d._plan for d in mods), bool(upsample_last), int(time))
+    cfg = (plans, bool(upsample_last), int(time))
     return _DecodeSideFn.apply(cfg, save, *z_vqs, *ys, *flat)
 
 
-class Model(nn.Module):
+class Model(HierModelBase):
     """`Model(arch)` with the reference's keys: levels (1..3), use_gst (false
     at levels == 1), use_ema, y_num, y_dim, jitter_p, beta, pooling_last,
     upsample_last, encoder.{i}, decoder.{i}, quantizer.{i}, final_decoder
@@ -155,14 +150,15 @@ class Model(nn.Module):
     y_idx[..., :1]): xhat, loss, loss dict from one readback at the end.
     encode(x) restates :52-70; decode((zs, ys), time) restates :73-90 with ys
     (B, levels), level i rendered with speaker ys[:, i]; infer((x, ys)) is the
-    two together.  convert((x, y_idx)) is the xhat of the eval-mode forward,
-    as vqvae2a.Model.convert.  encode, decode, infer and convert run without
-    gradients and write no parameter or buffer.
+    two together.  convert((x, y_idx)) is the xhat of the eval-mode forward
+    (encode and convert are HierModelBase's).  encode, decode, infer and
+    convert run without gradients and write no parameter or buffer.
 
     Refused at construction: jitter_p != 0 with a mean-pooled quantized top
     level (one frame has no neighbour), use_gst with pooling_last: false (the
     reference hands the style layer a 3-D tensor there and fails), and
     whatever vqvae2.Encoder / vqvae2.Decoder refuse."""
+    name = "vqvae2b.Model"
 
     def __init__(self, arch):
         super().__init__()
@@ -205,25 +201,6 @@ class Model(nn.Module):
         self.upsample_last = arch.get("upsample_last", False)
         self.levels, self.use_gst, self.use_ema = levels, use_gst, use_ema
         self.compute_dtype = dtype
-        self._engine = None
-
-    # the optimizer engine (flat parameters, multi-tensor clip + Adam / RAdam; data
-    # parallel refused) and the weight-norm removal are vqvae2.Model's
-    engine = _Vqvae2Model.engine
-    remove_weight_norm = _Vqvae2Model.remove_weight_norm
-
-    def _is_style(self, i):
-        return self.use_gst and i == self.levels - 1
-
-    def _pooled(self, i):
-        return self.pooling_last and i == self.levels - 1
-
-    def _check(self, x):
-        if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != self.encoders[0].in_ch:
-            raise ValueError(f"vqvae2b.Model: x must be (B, {self.encoders[0].in_ch}, T)")
-        if not x.is_cuda:
-            raise L.VqxError("vqvae2b.Model runs on the MI355X only (libvqx); move it and its inputs with .cuda()")
-        return x.float().contiguous()
 
     def forward(self, input):
         """(x (B, mel, T), y_idx (B, 1)) -> (xhat (B, mel, T), loss, loss dict).
@@ -232,7 +209,7 @@ class Model(nn.Module):
         detail and quanti_err.k, as vqvae2a.Model.forward."""
         x, y_idx = input
         x = self._check(x)
-        z_vqs, ys, level_losses, enc_losses, details = [], [], [], [], []
+        z_vqs, ys, level_losses, enc_losses, named = [], [], [], [], []
         feat = x
         for i in range(self.levels):
             z, feat = self.encoders[i](feat)
@@ -243,45 +220,14 @@ class Model(nn.Module):
                 if self._pooled(i):
                     z = mean_pool(z)
                 z_vq, lvl, _, z_enc, detail = q(z, loss_weights=(1.0, self.beta), src_t=self.jitter.draw(z.shape[2]))
+                named += self._detail_scalars(len(level_losses), detail, z_enc)
                 level_losses.append(lvl)
                 enc_losses.append(z_enc)
-                details.append(dict(detail, quanti_err=z_enc))
             z_vqs.append(z_vq)
             ys.append(self.embeds[i](y_idx[..., :1]).reshape(x.shape[0], -1))  # (B, y_dim): one frame, never stretched
         xhat = decode_side(self.decoders, self.final_decoder, z_vqs, ys, x.shape[2], self.upsample_last)
-        x_loss = _LogLossFn.apply(xhat, x)
-        loss = x_loss
-        for lvl in level_losses:
-            loss = loss + lvl
-        vq = enc_losses[0]
-        for t in enc_losses[1:]:
-            vq = vq + t
-        names, scalars = ["Total", "VQ loss", "X like"], [loss.detach(), vq, x_loss.detach()]
-        for k, d in enumerate(details):
-            for key, val in d.items():
-                names.append(f"{key}.{k}")
-                scalars.append(val.detach())
-        host = torch.stack([s.reshape(()) for s in scalars]).tolist()  # the step's one readback
-        return xhat, loss, dict(zip(names, host))
-
-    def encode(self, input):
-        """vqvae2b.py:52-70: one entry per level, int64 indices (B, T_i) of a
-        quantized level, the style embedding (B, F, 1) of a style-token top.
-        Without gradients; writes nothing."""
-        x = input[0] if isinstance(input, (list, tuple)) else input
-        x = self._check(x)
-        zs = []
-        with torch.no_grad():
-            for i in range(self.levels):
-                z, x = self.encoders[i](x)
-                q = self.quantizers[i]
-                if self._is_style(i):
-                    zs.append(q.pool_forward(z).unsqueeze(-1))
-                else:
-                    if self._pooled(i):
-                        z = mean_pool(z)
-                    zs.append(q.encode(z))
-        return zs
+        loss, losses = self._loss(xhat, x, level_losses, enc_losses, named)
+        return xhat, loss, losses
 
     def _check_decode(self, zs, ys, time):
         """decode's validation on the host, before any libvqx launch of its own
@@ -290,17 +236,14 @@ class Model(nn.Module):
         zs = list(zs)
         if len(zs) != self.levels or not all(torch.is_tensor(z) for z in zs):
             raise ValueError(f"{who}: zs must hold one tensor per level ({self.levels})")
-        B, spans = zs[0].shape[0], []
+        B = zs[0].shape[0]
         for i, z in enumerate(zs):
             if self._is_style(i):
                 if z.dim() != 3 or not z.is_floating_point() or z.shape[1] != self.decoders[i].layers[0].cin:
                     raise ValueError(f"{who}: level {i} is a style level: a float (B, "
                                      f"{self.decoders[i].layers[0].cin}, T_i) tensor")
-            else:
-                if z.dim() != 2 or z.dtype != torch.int64:
-                    raise ValueError(f"{who}: level {i} is a quantized level: int64 indices (B, T_i)")
-                if z.numel():
-                    spans += list(torch.aminmax(z))
+            elif z.dim() != 2 or z.dtype != torch.int64:
+                raise ValueError(f"{who}: level {i} is a quantized level: int64 indices (B, T_i)")
             if z.shape[0] != B or z.shape[-1] < 1:
                 raise ValueError(f"{who}: level {i} has shape {tuple(z.shape)}; level 0 has batch size {B}")
         if not torch.is_tensor(ys) or ys.dim() != 2 or tuple(ys.shape) != (B, self.levels) or ys.dtype != torch.int64:
@@ -313,16 +256,10 @@ class Model(nn.Module):
             except ValueError:
                 raise ValueError(f"{who}: level {i} has {z.shape[-1]} frames, which do not stretch to T = {T} "
                                  "(1 <= T_i <= T)") from None
-        ext = torch.stack(spans + list(torch.aminmax(ys))).tolist()  # the one readback
-        quantized = [i for i in range(self.levels) if not self._is_style(i) and zs[i].numel()]
-        for k, i in enumerate(quantized):
-            K = self.quantizers[i].z_num
-            if ext[2 * k] < 0 or ext[2 * k + 1] >= K:
-                raise ValueError(f"{who}: level {i} has indices in {ext[2 * k]}..{ext[2 * k + 1]}, the codebook "
-                                 f"holds 0..{K - 1}")
+        lo, hi = self._check_index_ranges(who, zs, ys)
         y_num = self.embeds[0].cond_num
-        if ext[-2] < 0 or ext[-1] >= y_num:
-            raise ValueError(f"{who}: ys has speakers in {ext[-2]}..{ext[-1]}, the model has 0..{y_num - 1}")
+        if lo < 0 or hi >= y_num:
+            raise ValueError(f"{who}: ys has speakers in {lo}..{hi}, the model has 0..{y_num - 1}")
         return zs, B, T
 
     def decode(self, input, time=None):
@@ -336,47 +273,26 @@ class Model(nn.Module):
         zs, ys = input
         zs, B, T = self._check_decode(zs, ys, time)
         if not all(z.is_cuda for z in zs) or not ys.is_cuda:
-            raise L.VqxError("vqvae2b.Model runs on the MI355X only (libvqx); move it and its inputs with .cuda()")
-        dt = _DT[self.compute_dtype]
+            raise self._off_device()
+        dt = DT[self.compute_dtype]
         with torch.no_grad():
             outs = []
             for i in range(self.levels):
-                z, q, dec = zs[i], self.quantizers[i], self.decoders[i]
+                z, dec = zs[i], self.decoders[i]
                 Td = z.shape[-1] if self.upsample_last else T
                 if self._is_style(i):
-                    level = z.float().reshape(B, -1) if z.shape[2] == 1 else _to_rows(z)
+                    level = z.float().reshape(B, -1) if z.shape[2] == 1 else to_rows(z)
                 else:
-                    z = z.contiguous()
-                    if z.data_ptr() % 16:  # a slice of a longer index tensor: the kernel reads aligned pointers
-                        z = z.clone()
-                    level = (z, q.embeddings.detach(), bool(getattr(q, "normalize", False)))
+                    level = self._index_level(i, z)
                 rows = torch.empty(B * Td, dec.layers[0].cin, device=ys.device, dtype=dt)
                 ops.codes_upsample_cat([level], B, Td, rows)
                 y = self.embeds[i](ys[:, i:i + 1]).reshape(B, -1)
                 outs.append(dec.forward_rows(rows, B, Td, [y]))
             joined = torch.empty(B * T, sum(o.shape[1] for o in outs), device=ys.device, dtype=dt)
             ops.upsample_cat_fwd(outs, B, T, joined)
-            return _to_nct(self.final_decoder.forward_rows(joined, B, T, None), B, T)
+            return to_nct(self.final_decoder.forward_rows(joined, B, T, None), B, T)
 
     def infer(self, input):
         """(x, ys (B, levels)) -> decode((encode(x), ys)) (vqvae2b.py:93-97)."""
         x, ys = input
         return self.decode((self.encode(x), ys))
-
-    def convert(self, input):
-        """(x (B, mel, T), y_idx (B, 1)) -> the xhat of the eval-mode forward,
-        without gradients.  A normalised codebook, which every forward
-        renormalises in place, gets its bits back, so no parameter or buffer
-        changes (an EMA codebook is neither initialised nor updated in eval mode)."""
-        mutated = [q.embeddings for q in self.modules() if isinstance(q, VectorQuantizer) and q.normalize]
-        saved = [e.detach().clone() for e in mutated]
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                xhat = self.forward(input)[0]
-                for e, s in zip(mutated, saved):
-                    e.copy_(s)
-        finally:
-            self.train(was_training)
-        return xhat
