@@ -988,6 +988,14 @@ int vqx_vq_commit_bwd_g(const float* z, const float* zq, int32_t B, int32_t D, i
  *   never read.
  * vqx_segment_mean: out[b][c] = (sum_{t < len[b]} z[b*T + t][c]) / len[b], f32
  *   z [B*T][ldz] -> out [B][ldo], summed in a fixed order.
+ * vqx_nct_to_ntc_len / vqx_ntc_to_nct_len (the flat model's batched conversion):
+ *   vqx_nct_to_ntc / vqx_ntc_to_nct with the tail mask in the same pass.
+ *     y[b*T + t][c] = t < len[b] ? cvt(x_nct[b][c][t]) : 0          (x f32 (B, C, T))
+ *     x_nct[b][c][t] = t < len[b] ? float(y[b*T + t][c]) : 0, t < T_out <= T
+ *                                                          (x f32 (B, C, T_out))
+ *   The zero is selected, not multiplied, and the source is not loaded at
+ *   t >= len[b]: it may hold anything there, NaN included.  Any C >= 1,
+ *   ldy >= C; pointers aligned to their element.
  */
 int vqx_groupnorm_stats_len(const void* x, int32_t ldx, int32_t dtype, int64_t n_rows, int32_t T, int32_t C,
                             int32_t G, const int32_t* len, float eps, float* partials, float* mean_rstd,
@@ -1005,6 +1013,10 @@ int vqx_codes_upsample_cat_len(const vqx_codes_level* levels, int32_t n_levels, 
                                vqx_stream_t stream);
 int vqx_segment_mean(const float* z, int32_t ldz, int64_t n_rows, int32_t T, int32_t C, const int32_t* len,
                      float* out, int32_t ldo, vqx_stream_t stream);
+int vqx_nct_to_ntc_len(const float* x_nct, int32_t B, int32_t C, int32_t T, const int32_t* len, void* y, int32_t ldy,
+                       int32_t dtype, vqx_stream_t stream);
+int vqx_ntc_to_nct_len(const void* y, int32_t ldy, int32_t dtype, int32_t B, int32_t C, int32_t T, const int32_t* len,
+                       float* x_nct, int32_t T_out, vqx_stream_t stream);
 
 /* ABI 130: vqx_conv_args.rowbias_T appended (segmented row bias of the forward
  * epilogue; 0 or 1 keeps every earlier call's bits) and vqx_upsample_cat_*. */

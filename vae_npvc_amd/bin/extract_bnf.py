@@ -9,8 +9,16 @@ bin/extract_bnf.py:22-67 on this package's model and Kaldi I/O.
 `token`: the (T, 1) index column.  Text output writes `utt <i><j>...` lines,
 otherwise a Kaldi archive of int32 vectors (WSPECIFIER `ark:...` or
 `ark,scp:...`).
+
+`--batch_size N` (default 1: the loop over single utterances, unchanged)
+encodes up to N utterances per call as one padded batch, `model.encode(x,
+lengths=...)`.  Utterances are read `N * WINDOW_BATCHES` at a time in input
+order, sorted by length inside that window and cut into batches of N
+neighbours (decoder.basic.length_batches); a batch's index tensor is copied to
+the host once and cut per utterance there; the window is written in input order.
 """
 import argparse
+import inspect
 import os
 from importlib import import_module
 
@@ -19,6 +27,34 @@ import torch
 import yaml
 
 from ..dataset.kaldi_io import ReadHelper, WriteHelper
+from ..decoder.basic import WINDOW_BATCHES, length_batches
+
+
+def bnf_of(ids, kind):
+    """One utterance's output from its own frame indices `ids` (a 1-D host int64 array)."""
+    if kind == "id":
+        return ids
+    if kind == "csid":  # consecutive duplicates merged (unique_consecutive)
+        return ids[np.concatenate([[True], ids[1:] != ids[:-1]])]
+    if kind == "token":
+        return ids.reshape(-1, 1)
+    raise ValueError(f"unknown bnf_kind {kind!r}")
+
+
+def encode_window(model, feats, N):
+    """feats: (T_b, mel) host arrays of one window -> their frame indices (host int64 arrays), in the same order."""
+    S = model.down_scale()
+    done = [None] * len(feats)
+    for pick in length_batches([f.shape[0] for f in feats], N):
+        lens = [feats[k].shape[0] for k in pick]
+        x = np.zeros((len(pick), feats[pick[0]].shape[1], max(lens)), dtype=np.float32)
+        for b, k in enumerate(pick):
+            x[b, :, :lens[b]] = feats[k].T
+        with torch.no_grad():
+            idx = model.encode(torch.from_numpy(x).cuda(), lengths=lens).cpu().numpy()  # the batch's one read-back
+        for b, k in enumerate(pick):
+            done[k] = idx[b, :lens[b] // S].copy()
+    return done
 
 
 def extract_bnf(args):
@@ -35,7 +71,33 @@ def extract_bnf(args):
     else:
         writer = WriteHelper(args.wspecifier)
         output_txt = False
-    n = 0
+
+    def put(utt, out):
+        if output_txt:
+            writer.write("{} {}\n".format(utt, "".join("<{}>".format(b) for b in out.reshape(-1))))
+        else:
+            writer.write(utt, out.astype(np.int32))
+
+    N, n = args.batch_size, 0
+    if N > 1:
+        if "lengths" not in inspect.signature(model.encode).parameters:
+            raise NotImplementedError(f"--batch_size {N}: {type(model).__module__}.Model.encode takes no `lengths`")
+        window = []
+
+        def flush():
+            for (utt, _), ids in zip(window, encode_window(model, [f for _, f in window], N)):
+                put(utt, bnf_of(ids, args.bnf_kind))
+            window.clear()
+
+        for utt, feat in ReadHelper(args.rspecifier):
+            window.append((utt, np.array(feat, dtype=np.float32)))
+            n += 1
+            if len(window) == N * WINDOW_BATCHES:
+                flush()
+        if window:
+            flush()
+        writer.close()
+        return n
     for utt, feat in ReadHelper(args.rspecifier):
         feat_in = torch.from_numpy(np.array(feat)).float().cuda().t().unsqueeze(0)
         with torch.no_grad():
@@ -48,25 +110,35 @@ def extract_bnf(args):
             out = bnf[0].cpu().numpy()
         else:
             raise ValueError(f"unknown bnf_kind {args.bnf_kind!r}")
-        if output_txt:
-            writer.write("{} {}\n".format(utt, "".join("<{}>".format(b) for b in out.reshape(-1))))
-        else:
-            writer.write(utt, out.astype(np.int32))
+        put(utt, out)
         n += 1
     writer.close()
     return n
 
 
-def main(argv=None):
+def _positive(text):
+    n = int(text)
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"--batch_size must be a positive integer, got {text!r}")
+    return n
+
+
+def parser():
     p = argparse.ArgumentParser()
     p.add_argument("-c", "--config", type=str, required=True)
     p.add_argument("--model_path", type=str, default=None)
     p.add_argument("--bnf_kind", type=str, default="id")
     p.add_argument("--output_txt", type=str, default="true")
     p.add_argument("--gpu", type=str, default=None)
+    p.add_argument("--batch_size", type=_positive, default=1,
+                   help="utterances per padded batch (1: one utterance per call)")
     p.add_argument("rspecifier", type=str)
     p.add_argument("wspecifier", type=str)
-    args = p.parse_args(argv)
+    return p
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
     if args.gpu is not None:
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu
     return extract_bnf(args)

@@ -27,6 +27,10 @@
 //   segment_mean_kernel    out[b][c] = (sum_{t < len[b]} z[b*T + t][c]) / len[b]:
 //             16 row groups (rows rg, rg + 16, ... added in ascending t from
 //             0.f), the 16 sums added in ascending rg from 0.f, one division.
+//   nct_to_ntc_len_kernel / ntc_to_nct_len_kernel  the flat model's two layout
+//             changes with the tail mask folded in (the 32 x 32 LDS tile of
+//             nct_to_ntc_tile; the utterance is blockIdx.z): frames t >= len[b]
+//             are selected zeros and their source is never loaded.
 // No atomics anywhere; equal arguments give equal bits.
 #include "vqx_common.h"
 #include "vqx_vec.h"
@@ -269,6 +273,65 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(const float* __restri
   }
 }
 
+// nct_to_ntc_tile (vqx_common.h) with the tail mask folded in: one 32 x 32 tile
+// a workgroup (blockIdx.x over T, .y over C, .z the utterance of this launch).
+// A frame t >= len[b] gets a selected 0.f and is never loaded; a tile wholly
+// past len[b] stores its zeros without touching x or the LDS.
+template <typename T>
+__global__ __launch_bounds__(256) void nct_to_ntc_len_kernel(const float* __restrict__ x, int C, int T_, LenTable L,
+                                                             T* __restrict__ y, int64_t ldy) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z;
+  const int len = L.len[b];
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 256 threads: 8 rows per pass
+  if (t0 >= len) {  // workgroup-uniform
+    for (int i = ty; i < 32; i += 8) {
+      const int t = t0 + i, c = c0 + tx;
+      if (c < C && t < T_) Elem<T>::st(y, ((int64_t)b * T_ + t) * ldy + c, 0.f);
+    }
+    return;
+  }
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    tile[i][tx] = (c < C && t < len) ? x[((int64_t)b * C + c) * T_ + t] : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    if (c < C && t < T_) Elem<T>::st(y, ((int64_t)b * T_ + t) * ldy + c, tile[tx][i]);
+  }
+}
+
+// ntc_to_nct_kernel (vqx_layout.hip) with the tail mask folded in and the output
+// cut to T_out <= T frames (blockIdx.x over T_out): rows t >= len[b] of y are
+// never loaded, whatever they hold.
+template <typename T>
+__global__ __launch_bounds__(256) void ntc_to_nct_len_kernel(const T* __restrict__ y, int64_t ldy, int C, int T_,
+                                                             LenTable L, float* __restrict__ x, int T_out) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z;
+  const int len = L.len[b];
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  if (t0 >= len) {  // workgroup-uniform
+    for (int i = ty; i < 32; i += 8) {
+      const int c = c0 + i, t = t0 + tx;
+      if (c < C && t < T_out) x[((int64_t)b * C + c) * T_out + t] = 0.f;
+    }
+    return;
+  }
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    tile[i][tx] = (c < C && t < len) ? Elem<T>::ld(y, ((int64_t)b * T_ + t) * ldy + c) : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    if (c < C && t < T_out) x[((int64_t)b * C + c) * T_out + t] = tile[tx][i];
+  }
+}
+
 bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // Every item before any launch: len[b] in 1..T.
@@ -291,6 +354,24 @@ LenTable table_at(const int32_t* len, int b0, int n) {
 }
 
 int blocks_for(int64_t chunks) { return (int)std::min<int64_t>(std::max<int64_t>((chunks + 255) / 256, 1), 1024); }
+
+// Checks shared by the two layout changes (C channels of a [B*T][ldy] matrix): 0 when the launches may go.
+int check_layout(const char* who, const void* x, const void* y, int B, int C, int T, int ldy, int dtype,
+                 const int32_t* len, int& Bc) {
+  if (B < 1) { set_error("%s: B = %d utterances", who, B); return -1; }
+  if (check_lens(who, len, (int64_t)B * T, T, Bc)) return -1;
+  if (dtype != VQX_F32 && dtype != VQX_BF16) { set_error("%s: bad dtype %d", who, dtype); return -1; }
+  const uintptr_t ya = dtype == VQX_BF16 ? 1 : 3;
+  if (!x || !y || ((uintptr_t)x & 3) || ((uintptr_t)y & ya)) {
+    set_error("%s: null or unaligned pointer (f32 4 B, bf16 2 B)", who);
+    return -1;
+  }
+  if (C < 1 || (C + 31) / 32 > 65535 || ldy < C) {
+    set_error("%s: C = %d, ldy = %d (1 <= C <= %d, ldy >= C)", who, C, ldy, 65535 * 32);
+    return -1;
+  }
+  return 0;
+}
 
 }  // namespace
 }  // namespace vqx
@@ -491,6 +572,51 @@ extern "C" int vqx_segment_mean(const float* z, int32_t ldz, int64_t n_rows, int
     const LenTable L = table_at(len, b0, n);
     hipLaunchKernelGGL(segment_mean_kernel, dim3((C + 63) / 64, n), dim3(256), 0, s, z + (int64_t)b0 * T * ldz,
                        (int64_t)ldz, T, C, L, out + (int64_t)b0 * ldo, (int64_t)ldo);
+  }
+  return launch_status(who);
+}
+
+extern "C" int vqx_nct_to_ntc_len(const float* x_nct, int32_t B, int32_t C, int32_t T, const int32_t* len, void* y,
+                                  int32_t ldy, int32_t dtype, vqx_stream_t stream) {
+  const char* who = "vqx_nct_to_ntc_len";
+  int Bc;
+  if (check_layout(who, x_nct, y, B, C, T, ldy, dtype, len, Bc)) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t esz = dtype == VQX_BF16 ? 2 : 4;
+  for (int b0 = 0; b0 < B; b0 += kLenItems) {
+    const int n = std::min(kLenItems, B - b0);
+    const LenTable L = table_at(len, b0, n);
+    const dim3 grid((unsigned)((T + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)n);
+    const float* xb = x_nct + (int64_t)b0 * C * T;
+    char* yb = (char*)y + (int64_t)b0 * T * ldy * esz;
+    if (dtype == VQX_BF16)
+      hipLaunchKernelGGL(nct_to_ntc_len_kernel<bf16_t>, grid, dim3(256), 0, s, xb, C, T, L, (bf16_t*)yb, (int64_t)ldy);
+    else
+      hipLaunchKernelGGL(nct_to_ntc_len_kernel<float>, grid, dim3(256), 0, s, xb, C, T, L, (float*)yb, (int64_t)ldy);
+  }
+  return launch_status(who);
+}
+
+extern "C" int vqx_ntc_to_nct_len(const void* y, int32_t ldy, int32_t dtype, int32_t B, int32_t C, int32_t T,
+                                  const int32_t* len, float* x_nct, int32_t T_out, vqx_stream_t stream) {
+  const char* who = "vqx_ntc_to_nct_len";
+  int Bc;
+  if (check_layout(who, x_nct, y, B, C, T, ldy, dtype, len, Bc)) return -1;
+  if (T_out < 1 || T_out > T) { set_error("%s: T_out = %d outside [1, T = %d]", who, T_out, T); return -1; }
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t esz = dtype == VQX_BF16 ? 2 : 4;
+  for (int b0 = 0; b0 < B; b0 += kLenItems) {
+    const int n = std::min(kLenItems, B - b0);
+    const LenTable L = table_at(len, b0, n);
+    const dim3 grid((unsigned)((T_out + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)n);
+    const char* yb = (const char*)y + (int64_t)b0 * T * ldy * esz;
+    float* xb = x_nct + (int64_t)b0 * C * T_out;
+    if (dtype == VQX_BF16)
+      hipLaunchKernelGGL(ntc_to_nct_len_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)yb, (int64_t)ldy, C, T, L,
+                         xb, T_out);
+    else
+      hipLaunchKernelGGL(ntc_to_nct_len_kernel<float>, grid, dim3(256), 0, s, (const float*)yb, (int64_t)ldy, C, T, L, xb,
+                         T_out);
   }
   return launch_status(who);
 }

@@ -1097,8 +1097,16 @@ class VQVAEEngine:
         self.n_fused_prologue = getattr(self, "n_fused_prologue", 0) + 1
         return True
 
-    def encoder_fwd(self, w, x_nct, transposed=False):
-        if not transposed:
+    def encoder_fwd(self, w, x_nct, transposed=False, lens=None):
+        """lens (inference only, a list of host ints): utterance b owns frames
+        t < lens[b] of the padded batch.  Every operand of a multi-tap conv then
+        has zero rows from its utterance's end up (DESIGN.md "Flat model: a batch
+        of different lengths"): the GroupNorm statistics come from the *_len
+        kernels over the valid rows, never from the GEMM tiles, and the
+        LeakyReLU outputs the next convs read get a zero tail."""
+        if lens is not None:
+            ops.nct_to_ntc_len(x_nct, lens, w.x)  # the input's padding is never read
+        elif not transposed:
             ops.nct_to_ntc(x_nct, w.x)
         inp, T_in = w.x, w.T
         for si, st in enumerate(self.enc_stages):
@@ -1107,13 +1115,19 @@ class VQVAEEngine:
             # every GEMM producing c_j also writes a_j = LeakyReLU(c_j), the operand
             # of the next conv stack / stage conv / output conv (vqvae.py:171, layers.py:152)
             self.fwd(st.conv, inp, sw.c[0], T_in, bias=st.conv.mod.bias, act=L.PRO_LRELU, y2=sw.a[0])
+            if lens is not None:
+                lens = [n // st.scale for n in lens]
+                ops.mask_tail(sw.a[0], T, lens)
             for j, b in enumerate(st.blocks):
                 src = sw.a[j]
                 gkw = {}
                 for l, (Lr, gn) in enumerate(zip(b.convs, b.gns)):
                     h, mr = sw.h[j][l], sw.mr[j][l]
                     last = l == st.L - 1
-                    if sw.fuse:  # statistics of h from the GEMM's epilogue tiles
+                    if lens is not None:  # statistics over each utterance's own rows
+                        self.fwd(Lr, src, h, T, bias=Lr.mod.bias)
+                        ops.groupnorm_stats_len(h, T, 1, lens, w.gn_part, mr)
+                    elif sw.fuse:  # statistics of h from the GEMM's epilogue tiles
                         self.fwd(Lr, src, h, T, bias=Lr.mod.bias, gn_stats=w.gst, gn_groups=1)
                         if last and not self._enc_gn_separate:
                             gkw = dict(gn_tiles=w.gst)  # merged inside the skip GEMM
@@ -1123,23 +1137,38 @@ class VQVAEEngine:
                         self.fwd(Lr, src, h, T, bias=Lr.mod.bias)
                         ops.groupnorm_stats(h, T, 1, w.gn_part, mr)
                     if not last:  # LeakyReLU(GN(h)): the next conv's operand (layers.py:156-161)
-                        ops.gn_lrelu_fwd(h, sw.g[j][l], T, mr, gn.weight, gn.bias)
+                        if lens is not None:
+                            ops.gn_lrelu_fwd_len(h, sw.g[j][l], T, lens, mr, gn.weight, gn.bias)
+                        else:
+                            ops.gn_lrelu_fwd(h, sw.g[j][l], T, mr, gn.weight, gn.bias)
                         src = sw.g[j][l]
                 gn = b.gns[-1]
                 self.fwd(b.skip, sw.c[j], sw.c[j + 1], T, bias=b.skip.mod.bias, gn_h=sw.h[j][-1], gn_mr=sw.mr[j][-1],
                          gn_gamma=gn.weight, gn_beta=gn.bias, act=L.PRO_LRELU, y2=sw.a[j + 1], **gkw)
+                if lens is not None:
+                    ops.mask_tail(sw.c[j + 1], T, lens)
+                    ops.mask_tail(sw.a[j + 1], T, lens)
             inp, T_in = sw.a[-1], T
         self.fwd(self.enc_out, inp, w.z, T_in, bias=self.enc_out.mod.bias, out_f32=True)
 
-    def decoder_fwd(self, w, zq_c):
+    def decoder_fwd(self, w, zq_c, lens=None):
+        """lens (inference only): the utterances' lengths at zq_c's rate; zq_c
+        must hold zero rows from each utterance's end up (encoder_fwd, lens)."""
         inp, T_in = zq_c, w.Tz
         for si, st in enumerate(self.dec_stages):
             sw = w.dec[si]
             T, C = sw.T, sw.C
             self.fwd(st.conv, inp, sw.xs[0], T_in, bias=st.conv.mod.bias)
+            if lens is not None:
+                lens = [n * st.scale for n in lens]
+                ops.mask_tail(sw.xs[0], T, lens)  # its tail holds the bias
             for j, b in enumerate(st.blocks):
                 ci, gn, rs = b.conv_in, b.gn, b.rs
-                if sw.fuse:  # statistics from the GEMM's epilogue tiles, finalised inside the GLU launch
+                if lens is not None:  # statistics and apply over each utterance's own rows; g gets a zero tail
+                    self.fwd(ci, sw.xs[j], sw.u[j], T, bias=ci.mod.bias, rowbias=sw.condbias[j])
+                    ops.groupnorm_stats_len(sw.u[j], T, 2, lens, w.gn_part, sw.mr[j])
+                    ops.gn_glu_fwd_len(sw.u[j], sw.g[j], T, lens, sw.mr[j], gn.weight, gn.bias)
+                elif sw.fuse:  # statistics from the GEMM's epilogue tiles, finalised inside the GLU launch
                     self.fwd(ci, sw.xs[j], sw.u[j], T, bias=ci.mod.bias, rowbias=sw.condbias[j], gn_stats=w.gst,
                              gn_groups=2)
                     ops.gn_glu_fwd_tiles(sw.u[j], sw.g[j], T, w.gst, sw.mr[j], gn.weight, gn.bias)
@@ -1149,8 +1178,11 @@ class VQVAEEngine:
                     ops.gn_glu_fwd(sw.u[j], sw.g[j], T, sw.mr[j], gn.weight, gn.bias)
                 self.fwd(rs, sw.g[j], sw.xs[j + 1], T, bias=rs.mod.bias, res=sw.xs[j], out2=w.skip32, split_col=C,
                          out2_accumulate=(b.gidx > 0))
+                if lens is not None:  # the residual is the next multi-tap conv's operand
+                    ops.mask_tail(sw.xs[j + 1], T, lens)
             inp, T_in = sw.xs[-1], T
-        # final_layer = ReLU, conv, ReLU, conv on sqrt(1/len(layers)) * sum(skips) (vqvae.py:316-318)
+        # final_layer = ReLU, conv, ReLU, conv on sqrt(1/len(layers)) * sum(skips) (vqvae.py:316-318);
+        # row-local (1x1 convs), so it needs no mask: the layout change out of xhat drops the tails
         ops.scale_act_2d(w.skip32, w.a_skip, math.sqrt(1.0 / self.n_dec_layers), L.PRO_RELU)
         self.fwd(self.fin1, w.a_skip, w.f1, w.T, bias=self.fin1.mod.bias, act=L.PRO_RELU)
         self.fwd(self.fin2, w.f1, w.xhat, w.T, bias=self.fin2.mod.bias, out_f32=True)
@@ -2074,25 +2106,54 @@ class VQVAEEngine:
         ops.ntc_to_nct(w.xhat, w.xhat_nct)
         return w
 
-    def encode(self, x):
-        """Model.encode (vqvae.py:45-52): encoder + nearest-code index, (B, T_z) int64."""
+    LEN_PAD = 1  # frames (times the down-sampling product) the padded T of a batch with lengths is rounded up to
+
+    def len_frames(self, lens):
+        """The frame count a batch with these lengths runs at: max(lens) rounded
+        up to LEN_PAD times the down-sampling product.  A function of the
+        lengths alone, so encode and decode of one batch run the same shapes."""
+        g = self.LEN_PAD * math.prod(st.scale for st in self.enc_stages)
+        return -(-max(lens) // g) * g
+
+    def encode(self, x, lens=None):
+        """Model.encode (vqvae.py:45-52): encoder + nearest-code index, (B, T_z) int64.
+        lens (a list of host ints, validated by Model): a padded batch; the
+        quantizer runs on every row (it is row-local) and the indices from each
+        utterance's end up are replaced by 0: (B, max_b T_z,b)."""
         B, _, T = x.shape
+        if lens is not None:
+            Tw = self.len_frames(lens)
+            if T != Tw:  # the layout kernel reads x at the workspace's frame count
+                x = x[:, :, :Tw].contiguous() if T > Tw else torch.nn.functional.pad(x, (0, Tw - T))
+            T = Tw
         self._join()
         w = self._eval_ws(B, T)
         self.pack_weights()
-        self.encoder_fwd(w, x)
+        self.encoder_fwd(w, x, lens=lens)
         q = self.m.quantizer
         if self.plain:
-            return q.encode(w.z.view(B, w.Tz, -1), time_last=False)
-        ops.vq_forward(w.z, q.embeddings, w.idx, None, None, None, w.vq_part, None, None)
-        return w.idx.view(B, w.Tz).clone()
+            idx = q.encode(w.z.view(B, w.Tz, -1), time_last=False)
+        else:
+            ops.vq_forward(w.z, q.embeddings, w.idx, None, None, None, w.vq_part, None, None)
+            idx = w.idx.view(B, w.Tz)
+        if lens is None:
+            return idx if self.plain else idx.clone()
+        lz = [n * w.Tz // T for n in lens]
+        keep = (torch.arange(max(lz))[None, :] < torch.tensor(lz)[:, None]).to(self.device)
+        return torch.where(keep, idx[:, :max(lz)], torch.zeros((), dtype=idx.dtype, device=self.device))
 
-    def decode(self, z_idx, y):
-        """Model.decode (vqvae.py:55-60): codebook gather + decoder, (B, F, T) f32."""
+    def decode(self, z_idx, y, lens=None):
+        """Model.decode (vqvae.py:55-60): codebook gather + decoder, (B, F, T) f32.
+        lens (a list of host ints, validated by Model, which also replaced the
+        indices from each utterance's end up by 0): utterance b has lens[b]
+        output frames; (B, F, max(lens)) with zeros from lens[b] up."""
         B, Tz = z_idx.shape
-        T = Tz
-        for st in self.enc_stages:
-            T *= st.scale
+        S = math.prod(st.scale for st in self.enc_stages)
+        T = Tz * S
+        if lens is not None:
+            T = self.len_frames(lens)
+            if Tz != T // S:
+                z_idx = z_idx[:, :T // S] if Tz > T // S else torch.nn.functional.pad(z_idx, (0, T // S - Tz))
         self._join()
         w = self._eval_ws(B, T)
         w.y_dev = y.reshape(-1)
@@ -2101,6 +2162,12 @@ class VQVAEEngine:
         q = self.m.quantizer
         ops.gather_rows(q._codebook() if self.plain else q.embeddings, z_idx.reshape(-1).contiguous(), w.zq)
         ops.convert_2d(w.zq, w.zq_c)
-        self.decoder_fwd(w, w.zq_c)
-        ops.ntc_to_nct(w.xhat, w.xhat_nct)
-        return w.xhat_nct.clone()
+        if lens is None:
+            self.decoder_fwd(w, w.zq_c)
+            ops.ntc_to_nct(w.xhat, w.xhat_nct)
+            return w.xhat_nct.clone()
+        lz = [n // S for n in lens]
+        ops.mask_tail(w.zq_c, w.Tz, lz)  # a padded position gathered code 0
+        self.decoder_fwd(w, w.zq_c, lens=lz)
+        out = torch.empty(B, self.dims["F"], max(lens), device=self.device, dtype=F32)
+        return ops.ntc_to_nct_len(w.xhat, T, lens, out)

@@ -15,6 +15,8 @@ import math
 import torch
 import torch.nn as nn
 
+from .. import ops
+from .._lib import VqxError
 from ..engine.step import EngineOptions, VQVAEEngine
 from .layers import Conditions, ResidualBlock, ResSkipBlock, WNConv1d
 from .resample import ResampleConv1d
@@ -166,7 +168,6 @@ class Model(nn.Module):
             eng.vq_ema_update(w)  # update_emb runs inside the reference forward (layers_vq.py:295-296)
             stats = w.stats.clone()
             xhat = torch.empty_like(w.xhat_nct)
-            from .. import ops
             ops.ntc_to_nct(w.xhat, xhat)
             detail = eng.loss_detail(w, stats.cpu())
             return xhat, total, detail
@@ -177,17 +178,86 @@ class Model(nn.Module):
             detail["entropy"] = d["entropy"]
         return w.xhat_nct.clone(), torch.tensor(d["Total"], device=x.device), detail
 
-    def encode(self, input):
+    # ---- a batch of different lengths (DESIGN.md "Flat model: a batch of different lengths")
+    def down_scale(self):
+        """The product S of the encoder's down-sampling scales."""
+        return math.prod(getattr(self.encoder.encode[k], "scale", 1) for k in self.encoder.stage_index)
+
+    def _batch_lengths(self, who, lengths, B, T):
+        """`lengths` as a list of B host ints, each in 1..T and a multiple of S;
+        ValueError otherwise.  Host arithmetic only."""
+        lens = list(ops.len_array(lengths, B, f"{who} lengths"))
+        S = self.down_scale()
+        for b, n in enumerate(lens):
+            if not 1 <= n <= T:
+                raise ValueError(f"{who}: utterance {b}: length {n} outside 1..{T}")
+            if n % S:
+                raise ValueError(f"{who}: utterance {b}: length {n} is not a multiple of the down-sampling scale {S}")
+        return lens
+
+    @staticmethod
+    def _off_device(who):
+        return VqxError(f"{who} runs on the MI355X only (libvqx); move the model and its inputs with .cuda()")
+
+    def encode(self, input, lengths=None):
+        """x (B, mel, T) -> code indices (B, T_z) int64 (vqvae.py:45-52).
+
+        lengths (host values: a sequence of ints or a 1-D CPU int tensor): a
+        padded batch, utterance b owning frames t < lengths[b] <= T; whatever x
+        holds from lengths[b] on is never read.  Each length is a multiple of
+        the encoder's down-sampling product S.  Returns (B, max_b lengths[b]/S)
+        with 0 from lengths[b]/S up; every utterance gets the indices it would
+        get alone.  Under no_grad; validated on the host before any launch."""
         x = input[0] if isinstance(input, (list, tuple)) else input
-        return self.engine(x.device).encode(x.float().contiguous())
+        if lengths is None:
+            return self.engine(x.device).encode(x.float().contiguous())
+        who = "vqvae.Model.encode"
+        if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != self.encoder.in_ch:
+            raise ValueError(f"{who}: x must be (B, {self.encoder.in_ch}, T)")
+        lens = self._batch_lengths(who, lengths, x.shape[0], x.shape[2])
+        if not x.is_cuda:
+            raise self._off_device(who)
+        with torch.no_grad():
+            return self.engine(x.device).encode(x.float().contiguous(), lens)
 
-    def decode(self, input):
+    def decode(self, input, lengths=None):
+        """(indices (B, T_z), y (B, 1)) -> xhat (B, mel, T_z * S) f32 (vqvae.py:55-60).
+
+        lengths (host values, as encode): the indices of a padded batch as
+        encode(x, lengths) returns them, at least max_b lengths[b]/S wide;
+        entries from lengths[b]/S up are ignored.  Returns (B, mel,
+        max(lengths)) with exact zeros from lengths[b] up, every utterance
+        rendered as it would be alone.  Under no_grad; bad lengths or indices
+        raise ValueError before any launch (one read-back: the extremes of the
+        valid indices)."""
         z_idx, y_idx = input
-        return self.engine(z_idx.device).decode(z_idx, y_idx)
+        if lengths is None:
+            return self.engine(z_idx.device).decode(z_idx, y_idx)
+        who = "vqvae.Model.decode"
+        if not torch.is_tensor(z_idx) or z_idx.dim() != 2 or z_idx.dtype != torch.int64:
+            raise ValueError(f"{who}: the indices must be an int64 (B, T_z) tensor")
+        B, S = z_idx.shape[0], self.down_scale()
+        if not torch.is_tensor(y_idx) or y_idx.numel() != B:
+            raise ValueError(f"{who}: y must hold one speaker index per utterance ({B})")
+        lens = self._batch_lengths(who, lengths, B, 2 ** 31 - 1)  # the index width bounds them below
+        lz = [n // S for n in lens]
+        if z_idx.shape[1] < max(lz):
+            raise ValueError(f"{who}: the indices hold {z_idx.shape[1]} frames, the lengths need {max(lz)}")
+        keep = (torch.arange(max(lz))[None, :] < torch.tensor(lz)[:, None]).to(z_idx.device)
+        z_idx = torch.where(keep, z_idx[:, :max(lz)], torch.zeros((), dtype=torch.int64, device=z_idx.device))
+        lo, hi = torch.stack(torch.aminmax(z_idx)).tolist()  # the one read-back
+        K = self.quantizer.z_num
+        if lo < 0 or hi >= K:
+            raise ValueError(f"{who}: indices in {lo}..{hi}, the codebook holds 0..{K - 1}")
+        if not z_idx.is_cuda or not y_idx.is_cuda:
+            raise self._off_device(who)
+        with torch.no_grad():
+            return self.engine(z_idx.device).decode(z_idx, y_idx, lens)
 
-    def infer(self, input):
+    def infer(self, input, lengths=None):
+        """(x, y) -> decode((encode(x), y)); with lengths, of the padded batch (encode, decode)."""
         x, y_idx = input
-        return self.decode((self.encode(x), y_idx))
+        return self.decode((self.encode(x, lengths), y_idx), lengths)
 
     def remove_weight_norm(self):
         """vqvae.py:93-103: bake w = g*v/||v|| into a plain `weight` on every

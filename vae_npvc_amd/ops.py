@@ -1282,6 +1282,36 @@ def mask_tail(x, T, lengths):
     return x
 
 
+def nct_to_ntc_len(x_nct, lengths, y):
+    """y[b*T + t, c] = x_nct[b, c, t] for t < lengths[b], else 0 (vqx_nct_to_ntc_len):
+    nct_to_ntc and mask_tail in one pass; x_nct is not read from lengths[b] up."""
+    _check_cuda(x_nct, y)
+    if x_nct.dim() != 3 or x_nct.dtype != torch.float32 or not x_nct.is_contiguous():
+        raise ValueError("nct_to_ntc_len: x must be a contiguous f32 (B, C, T) tensor")
+    B, C, T = x_nct.shape
+    arr = len_array(lengths, B, "nct_to_ntc_len lengths")
+    if y.dim() != 2 or y.shape[0] != B * T or y.shape[1] < C or y.stride(1) != 1:
+        raise ValueError(f"nct_to_ntc_len: y must be [{B * T}, >= {C}] rows with unit column stride")
+    _rows(y, B * T, y.stride(0), C, "nct_to_ntc_len y")
+    call("vqx_nct_to_ntc_len", ptr(x_nct), B, C, T, arr, ptr(y), y.stride(0), dt_code(y.dtype), stream_ptr())
+    return y
+
+
+def ntc_to_nct_len(y, T, lengths, x_nct):
+    """x_nct[b, c, t] = y[b*T + t, c] for t < lengths[b], else 0, over t < T_out = x_nct.shape[2] <= T
+    (vqx_ntc_to_nct_len): mask_tail and ntc_to_nct in one pass; the rows of y from lengths[b] up are not read."""
+    arr = _len_rows(y, T, lengths, "ntc_to_nct_len")
+    _check_cuda(x_nct)
+    B = len(arr)
+    if x_nct.dim() != 3 or x_nct.dtype != torch.float32 or not x_nct.is_contiguous() or x_nct.shape[0] != B \
+            or x_nct.shape[1] > y.shape[1] or not 1 <= x_nct.shape[2] <= T:
+        raise ValueError(f"ntc_to_nct_len: x must be a contiguous f32 ({B}, C <= {y.shape[1]}, T_out <= {T}) tensor")
+    C, T_out = x_nct.shape[1], x_nct.shape[2]
+    _rows(y, B * T, y.stride(0), C, "ntc_to_nct_len y")
+    call("vqx_ntc_to_nct_len", ptr(y), y.stride(0), dt_code(y.dtype), B, C, T, arr, ptr(x_nct), T_out, stream_ptr())
+    return x_nct
+
+
 def codes_upsample_cat_len(levels, B, T, lengths, level_lengths, out):
     """codes_upsample_cat for a padded batch (vqx_codes_upsample_cat_len): utterance
     b has lengths[b] <= T output frames and level_lengths[l][b] frames at level
