@@ -1647,6 +1647,99 @@ def test_gn_lrelu_fwd_matches_torch(dtype, B, T, C, ld):
     assert e <= bound, (e, bound)
 
 
+def _maxerr(a, b):
+    a, b = a.double().cpu(), b.double().cpu()
+    return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
+
+
+def _gn_glu_case(dtype, B, T, C, ld, gamma_scale=1.0):
+    """One vqx_gn_glu_fwd call (twice, into NaN-filled buffers with a sentinel row) and its references: the
+    statistics are float64 per (utterance, group) rounded to float32, the same values for the kernel and the
+    references, which evaluate tanh(GN(u)[:, :C/2]) * sigmoid(GN(u)[:, C/2:]) on the rounded inputs in float64
+    and in stock float32 on the CPU."""
+    ops = _ops()
+    half = C // 2
+    gen = torch.Generator(device="cpu").manual_seed(340 + C + T)
+    u = (torch.randn(B, T, C, generator=gen) * 1.5 + 0.3).to(dtype)
+    gamma, beta = torch.randn(C, generator=gen) * gamma_scale, torch.randn(C, generator=gen)
+    ug = u.double().view(B, T, 2, half)
+    mean = ug.mean(dim=(1, 3))
+    rstd = 1.0 / (ug.var(dim=(1, 3), unbiased=False) + 1e-5).sqrt()
+    mr = torch.stack([mean, rstd], dim=2).float().contiguous()  # [B, group, (mean, rstd)]
+
+    def ref(dt):
+        x = u.to(dt).view(B, T, 2, half)
+        n = (x - mr[:, None, :, 0:1].to(dt)) * mr[:, None, :, 1:2].to(dt)
+        pre = n * gamma.to(dt).view(2, half) + beta.to(dt).view(2, half)
+        return (torch.tanh(pre[:, :, 0]) * torch.sigmoid(pre[:, :, 1])).reshape(B * T, half), pre
+
+    (r64, pre64), (r32, _) = ref(torch.float64), ref(torch.float32)
+    h = torch.zeros(B * T, ld, device=DEV, dtype=dtype)
+    h[:, :C] = u.view(B * T, C).to(DEV)
+    outs = []
+    for _ in range(2):
+        whole, g = _guarded((B * T, ld), dtype)
+        ops.gn_glu_fwd(h[:, :C], g[:, :half], T, mr.to(DEV), gamma.to(DEV), beta.to(DEV))
+        torch.cuda.synchronize()
+        assert _sentinel_ok(whole) and bool(torch.isnan(g[:, half:]).all())
+        outs.append(g[:, :half].cpu())
+    assert torch.equal(outs[0], outs[1])  # a second call gives the same bits (no NaN: checked by the callers)
+    bound = max(4 * _maxerr(r32, r64), 16 * 2.0 ** -23) + (2.0 ** -8 if dtype == torch.bfloat16 else 0.0)
+    return outs[0], r64, pre64, bound
+
+
+# (B, T, C, ld) and the row-loop branches of gn_glu_fwd_vec_kernel each reaches.  A workgroup takes 16 frames; a
+# thread owns one 16-byte chunk (V = 4 fp32 / 8 bf16 channels) of rows rs, rs + nrs, ... of them, nrs = 256 /
+# (C / 2 / V) row slots:
+#   (3, 37, 64, 80)      nrs 32 / 64: slots 0..15 (0..14 in the last block of 15 rows) hold ONE row, the others NO row
+#   (1, 101, 1024, 1024) fp32 nrs 2: 8 rows a slot = a pair and 3 turns of the PAIR LOOP; last block of 5 rows: slot 0
+#                        a pair then the single TAIL row, slot 1 a PAIR only.  bf16 nrs 4: a pair and 1 turn of
+#                        the loop; last block: slot 0 a PAIR only, slots 1..3 ONE row
+#   (2, 50, 256, 272)    fp32 nrs 8: a PAIR only; last block of 4 rows: ONE row, slots 4..7 NO row.  bf16 nrs 16: ONE
+#                        row; last block: slots 4..15 NO row
+#   (1, 21, 2048, 2048)  fp32 nrs 1 (the widest row the entry point takes): 16 rows in one slot = a pair and 7 turns
+#                        of the PAIR LOOP; last block of 5 rows: a pair, one turn, the TAIL row.  bf16 nrs 2: a
+#                        pair and 3 turns; last block: slot 0 a pair then the TAIL row, slot 1 a PAIR only
+# Either dtype reaches all five branches (no row, one row, a pair, the pair loop, a tail row).
+GN_GLU_SHAPES = [(3, 37, 64, 80), (1, 101, 1024, 1024), (2, 50, 256, 272), (1, 21, 2048, 2048)]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("B,T,C,ld", GN_GLU_SHAPES)
+def test_gn_glu_fwd_matches_float64(dtype, B, T, C, ld):
+    """vqx_gn_glu_fwd, the base of test_gn_glu_fwd_tiles_equals_finalize_then_glu and of
+    test_gn_glu_fwd_len_is_the_plain_kernel_on_the_valid_rows, against float64 at ragged shapes (see
+    GN_GLU_SHAPES): max|got - f64| / max|f64| <= max(4 * err32, 16 * 2^-23), 2^-8 more for bf16 output, err32
+    being stock float32 torch's error of the same expression in that norm; rows of stride ld >= C, utterance
+    boundaries inside the 16-frame blocks, pad columns and the row behind the output untouched, every output
+    written, the same bits from a second call.  Measured error / bound on the MI355X: 0.137 (fp32), 0.513 (bf16)
+    at worst."""
+    got, r64, _, bound = _gn_glu_case(dtype, B, T, C, ld)
+    e = _maxerr(got, r64)
+    print(f"gn_glu_fwd {dtype} {(B, T, C, ld)}: err {e:.3g} bound {bound:.3g} ratio {e / bound:.3f}")
+    assert not bool(torch.isnan(got).any())
+    assert e <= bound, (e, bound)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_gn_glu_fwd_saturated_gates_stay_finite(dtype):
+    """gamma scaled by 40: the pre-activations pass +-88, where the kernel's exp overflows to +inf (and 1 / inf
+    = 0) or underflows to 0.  Every output is finite and within the bound of test_gn_glu_fwd_matches_float64;
+    where the float64 value is exactly 0 or +-1 the output is within one rounding of its type of it.  Measured
+    error / bound on the MI355X: 0.106 (fp32), 0.499 (bf16)."""
+    B, T, C, ld = GN_GLU_SHAPES[0]
+    got, r64, pre64, bound = _gn_glu_case(dtype, B, T, C, ld, gamma_scale=40.0)
+    assert float(pre64.max()) > 88.0 and float(pre64.min()) < -88.0
+    e = _maxerr(got, r64)
+    print(f"gn_glu_fwd saturated {dtype}: err {e:.3g} bound {bound:.3g} ratio {e / bound:.3f}")
+    assert bool(torch.isfinite(got).all())
+    assert e <= bound, (e, bound)
+    exact = (r64 == 0) | (r64.abs() == 1)
+    assert int(exact.sum()) >= 100
+    u_out = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -24
+    assert bool(((got.double() - r64).abs()[exact] <= u_out * r64.abs()[exact]).all())
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_time_gather_equals_indexing(dtype):
     """vqx_time_gather: y[b][t] = x[b][src_t[t]] for a jitter map (a third of
