@@ -996,6 +996,16 @@ int vqx_vq_commit_bwd_g(const float* z, const float* zq, int32_t B, int32_t D, i
  *   The zero is selected, not multiplied, and the source is not loaded at
  *   t >= len[b]: it may hold anything there, NaN included.  Any C >= 1,
  *   ldy >= C; pointers aligned to their element.
+ * vqx_nct_to_ntc_pad_len (vqvae2a / vqvae2b's batched conversion): the source
+ *   x f32 (B, C, T_in) is shorter than the T >= T_in rows every utterance gets
+ *   in y [B*T][ldy]:
+ *     y[b*T + t][c] = t < len[b] ? cvt(x_nct[b][c][t]) : 0, t < T, 1 <= len[b] <= T_in
+ *   One pass in place of a zero-padded copy, vqx_nct_to_ntc and vqx_mask_tail.
+ *   The zero is selected and x is not loaded at t >= len[b].  T < T_in -> -1.
+ * vqx_index_mask_len: out[b][t] = t < len[b] ? idx[b*T + t] : 0 over
+ *   t < T_out <= T, 1 <= len[b] <= T_out; idx int64 [B*T], out int64
+ *   (B, T_out), both 8-B aligned: the codes of a padded batch with zeros at the
+ *   padded positions.  idx is not loaded at t >= len[b].  T_out > T -> -1.
  */
 int vqx_groupnorm_stats_len(const void* x, int32_t ldx, int32_t dtype, int64_t n_rows, int32_t T, int32_t C,
                             int32_t G, const int32_t* len, float eps, float* partials, float* mean_rstd,
@@ -1017,6 +1027,10 @@ int vqx_nct_to_ntc_len(const float* x_nct, int32_t B, int32_t C, int32_t T, cons
                        int32_t dtype, vqx_stream_t stream);
 int vqx_ntc_to_nct_len(const void* y, int32_t ldy, int32_t dtype, int32_t B, int32_t C, int32_t T, const int32_t* len,
                        float* x_nct, int32_t T_out, vqx_stream_t stream);
+int vqx_nct_to_ntc_pad_len(const float* x_nct, int32_t B, int32_t C, int32_t T_in, int32_t T, const int32_t* len,
+                           void* y, int32_t ldy, int32_t dtype, vqx_stream_t stream);
+int vqx_index_mask_len(const int64_t* idx, int32_t B, int32_t T, const int32_t* len, int64_t* out, int32_t T_out,
+                       vqx_stream_t stream);
 
 /* ABI 130: vqx_conv_args.rowbias_T appended (segmented row bias of the forward
  * epilogue; 0 or 1 keeps every earlier call's bits) and vqx_upsample_cat_*. */

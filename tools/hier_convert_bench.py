@@ -20,7 +20,15 @@ range of utterances per second.  Every size's output is compared with size
 On a tree whose driver has no `decode_batch_size` only size 1 is measured (the
 baseline: `decode_batch_size: 1` must reproduce it).  A lab script, no
 pass/fail bar.
-Usage (GPU box): python tools/hier_convert_bench.py [--json OUT] [--dtype bf16] [--sizes 1,4,8,16,32]"""
+
+--model vqvae2a | vqvae2b measures those two models at the same dimensions
+(model_arch).  Their one-at-a-time conversion is the eval-mode forward, which
+takes only lengths that are multiples of the encoders' total down-sampling
+(64), so for them the lengths are drawn uniformly from the multiples of 64
+inside LEN_LO..LEN_HI (192..640); every size converts the same directory.  On
+a tree whose `convert` takes no `lengths` for these models give --sizes 1.
+Usage (GPU box): python tools/hier_convert_bench.py [--json OUT] [--dtype bf16] [--sizes 1,4,8,16,32]
+                                                    [--model vqvae2|vqvae2a|vqvae2b]"""
 import argparse
 import json
 import os
@@ -64,13 +72,41 @@ def recipe(dtype):
     }
 
 
-def make_dir(root):
-    """The synthetic decode directory; returns (path, the trials' lengths in trial order)."""
+GRANULE = 64  # the total down-sampling of the three encoders
+
+
+def model_arch(model, dtype):
+    """The config of --model: vqvae2 is the recipe; vqvae2a the same dimensions with EMA codebooks and the
+    decoders wired for its chain (decoder i reads level i and decoder i + 1's output, every one conditioned on
+    the speaker); vqvae2b the same with level decoders of final_channels 128 that read their own level alone and
+    an unconditioned final_decoder of the recipe's decoder.0 shape."""
+    cfg = recipe(dtype)
+    if model == "vqvae2":
+        return cfg
+    cfg.update(model_type=f"vae_npvc_amd.model.{model}", use_ema=True)
+    for i in (0, 1):
+        cfg[f"quantizer.{i}"] = dict(z_dim=128, z_num=512, mu=0.99)
+    if model == "vqvae2a":
+        for i, cin in enumerate((256, 256, 128)):
+            cfg[f"decoder.{i}"] = dict(cfg[f"decoder.{i}"], in_channels=[cin], cond_channels=128)
+    else:
+        cfg["final_decoder"] = dict(cfg["decoder.0"], cond_channels=0)
+        for i in range(3):
+            cfg[f"decoder.{i}"] = dict(cfg[f"decoder.{i}"], in_channels=[128], cond_channels=128, final_channels=128)
+    return cfg
+
+
+def make_dir(root, granule=1):
+    """The synthetic decode directory; returns (path, the trials' lengths in trial order).  granule > 1: the
+    lengths are multiples of it."""
     rng = np.random.default_rng(SEED)
     data = Path(root) / "eval"
     data.mkdir()
     n_src = TRIALS // 3
-    lens = rng.integers(LEN_LO, LEN_HI + 1, n_src)
+    if granule == 1:
+        lens = rng.integers(LEN_LO, LEN_HI + 1, n_src)
+    else:
+        lens = granule * rng.integers(-(-LEN_LO // granule), LEN_HI // granule + 1, n_src)
     with K.WriteHelper(f"ark,scp:{data}/feats.ark,{data}/feats.scp") as w:
         for u in range(n_src):
             w[f"utt{u:03d}"] = rng.standard_normal((int(lens[u]), MEL)).astype(np.float32)
@@ -87,19 +123,27 @@ def read_all(path):
             if line.strip()]
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
     ap.add_argument("--dtype", default="bf16", choices=["fp32", "bf16"])
     ap.add_argument("--sizes", default="1,4,8,16,32")
     ap.add_argument("--windows", type=int, default=WINDOWS)
-    a = ap.parse_args()
+    ap.add_argument("--model", default="vqvae2", choices=["vqvae2", "vqvae2a", "vqvae2b"])
+    return ap
+
+
+def main():
+    a = parser().parse_args()
     assert torch.cuda.is_available(), "hier_convert_bench needs the MI355X"
     work = tempfile.mkdtemp(prefix="hier_convert_bench_")
     try:
-        data, lens = make_dir(work)
+        data, lens = make_dir(work, 1 if a.model == "vqvae2" else GRANULE)
         torch.manual_seed(SEED)
-        dec = Decoder(recipe(a.dtype))
+        dec = Decoder(model_arch(a.model, a.dtype))
+        if a.model != "vqvae2":  # an EMA codebook is all zeros before its first training forward
+            for q in dec.model.quantizers[:2]:
+                q.embeddings.normal_()
         batched = hasattr(dec, "decode_batch_size")
         sizes = [int(s) for s in a.sizes.split(",")] if batched else [1]
 
@@ -128,16 +172,21 @@ def main():
         for _ in range(a.windows):
             for s in sizes:  # alternate: every size sees the same machine state
                 times[s].append(decode(s, "timed")[1])
+        dist = f"uniform integers {LEN_LO}..{LEN_HI}, seed {SEED}" if a.model == "vqvae2" else \
+            f"uniform multiples of {GRANULE} in {LEN_LO}..{LEN_HI}, seed {SEED}"
         res = {"dtype": a.dtype, "batched_driver": batched, "trials": TRIALS, "frames": sum(lens),
-               "lengths": {"distribution": f"uniform integers {LEN_LO}..{LEN_HI}, seed {SEED}", "min": min(lens),
+               "lengths": {"distribution": dist, "min": min(lens),
                            "max": max(lens), "mean": sum(lens) / len(lens)},
                "windows": a.windows, "sizes": {}}
+        if a.model != "vqvae2":  # the default's records keep their keys
+            res["model"] = a.model
         for s in sizes:
             ups = sorted(TRIALS / t for t in times[s])
             res["sizes"][str(s)] = {"utt_per_s_median": statistics.median(ups), "utt_per_s_min": ups[0],
                                     "utt_per_s_max": ups[-1], "decode_s": times[s],
                                     "max_rel_l2_vs_size_1": diff[s]}
-            print(f"{a.dtype} decode_batch_size {s}: median {statistics.median(ups):.1f} utt/s "
+            tag = "" if a.model == "vqvae2" else a.model + " "
+            print(f"{tag}{a.dtype} decode_batch_size {s}: median {statistics.median(ups):.1f} utt/s "
                   f"(min {ups[0]:.1f}, max {ups[-1]:.1f}); written features vs size 1: rel L2 <= {diff[s]:.2e}",
                   flush=True)
         if a.json:

@@ -231,6 +231,9 @@ _SIGS = {
     "vqx_nct_to_ntc_len": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p],
     "vqx_ntc_to_nct_len": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                            c_void_p],
+    "vqx_nct_to_ntc_pad_len": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32,
+                               c_void_p],
+    "vqx_index_mask_len": [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p],
     "vqx_ntc_to_nct_scale": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p],
     "vqx_nct_to_ntc_lrelu_bwd": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float, c_void_p,
                                  c_int32, c_int32, c_void_p],

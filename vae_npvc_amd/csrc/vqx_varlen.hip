@@ -31,6 +31,13 @@
 //             changes with the tail mask folded in (the 32 x 32 LDS tile of
 //             nct_to_ntc_tile; the utterance is blockIdx.z): frames t >= len[b]
 //             are selected zeros and their source is never loaded.
+//   nct_to_ntc_pad_len_kernel  nct_to_ntc_len_kernel for a source (B, C, T_in)
+//             shorter than the T >= T_in rows an utterance gets: the input
+//             layout change of vqvae2a / vqvae2b's batched conversion, whose
+//             padded frame count is a multiple of the encoders' down-sampling.
+//   index_mask_len_kernel  out[b][t] = t < len[b] ? idx[b*T + t] : 0 over
+//             t < T_out <= T, int64: the codes of a padded batch as `encode`
+//             returns them; entries from len[b] on are never loaded.
 // No atomics anywhere; equal arguments give equal bits.
 #include "vqx_common.h"
 #include "vqx_vec.h"
@@ -332,6 +339,44 @@ __global__ __launch_bounds__(256) void ntc_to_nct_len_kernel(const T* __restrict
   }
 }
 
+// nct_to_ntc_len_kernel with the source's frame count T_in apart from the row
+// count T_ >= T_in of an utterance (blockIdx.x over T_): len[b] <= T_in, so a
+// frame past the source is past len[b] and is a selected zero like any other.
+template <typename T>
+__global__ __launch_bounds__(256) void nct_to_ntc_pad_len_kernel(const float* __restrict__ x, int C, int T_in, int T_,
+                                                                 LenTable L, T* __restrict__ y, int64_t ldy) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z;
+  const int len = L.len[b];
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  if (t0 >= len) {  // workgroup-uniform
+    for (int i = ty; i < 32; i += 8) {
+      const int t = t0 + i, c = c0 + tx;
+      if (c < C && t < T_) Elem<T>::st(y, ((int64_t)b * T_ + t) * ldy + c, 0.f);
+    }
+    return;
+  }
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    tile[i][tx] = (c < C && t < len) ? x[((int64_t)b * C + c) * T_in + t] : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    if (c < C && t < T_) Elem<T>::st(y, ((int64_t)b * T_ + t) * ldy + c, tile[tx][i]);
+  }
+}
+
+// blockIdx.y = utterance, blockIdx.x strides over its T_out entries.
+__global__ __launch_bounds__(256) void index_mask_len_kernel(const int64_t* __restrict__ idx, int T_, LenTable L,
+                                                             int64_t* __restrict__ out, int T_out) {
+  const int b = blockIdx.y;
+  const int len = L.len[b];
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < T_out; t += gridDim.x * 256)
+    out[(int64_t)b * T_out + t] = t < len ? idx[(int64_t)b * T_ + t] : (int64_t)0;
+}
+
 bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // Every item before any launch: len[b] in 1..T.
@@ -617,6 +662,55 @@ extern "C" int vqx_ntc_to_nct_len(const void* y, int32_t ldy, int32_t dtype, int
     else
       hipLaunchKernelGGL(ntc_to_nct_len_kernel<float>, grid, dim3(256), 0, s, (const float*)yb, (int64_t)ldy, C, T, L, xb,
                          T_out);
+  }
+  return launch_status(who);
+}
+
+extern "C" int vqx_nct_to_ntc_pad_len(const float* x_nct, int32_t B, int32_t C, int32_t T_in, int32_t T,
+                                      const int32_t* len, void* y, int32_t ldy, int32_t dtype, vqx_stream_t stream) {
+  const char* who = "vqx_nct_to_ntc_pad_len";
+  int Bc;
+  if (check_layout(who, x_nct, y, B, C, T_in, ldy, dtype, len, Bc)) return -1;  // len[b] in 1..T_in
+  if (T < T_in || (int64_t)B * T > INT32_MAX) {
+    set_error("%s: T = %d rows an utterance for T_in = %d frames (T >= T_in, B*T below 2^31)", who, T, T_in);
+    return -1;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t esz = dtype == VQX_BF16 ? 2 : 4;
+  for (int b0 = 0; b0 < B; b0 += kLenItems) {
+    const int n = std::min(kLenItems, B - b0);
+    const LenTable L = table_at(len, b0, n);
+    const dim3 grid((unsigned)((T + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)n);
+    const float* xb = x_nct + (int64_t)b0 * C * T_in;
+    char* yb = (char*)y + (int64_t)b0 * T * ldy * esz;
+    if (dtype == VQX_BF16)
+      hipLaunchKernelGGL(nct_to_ntc_pad_len_kernel<bf16_t>, grid, dim3(256), 0, s, xb, C, T_in, T, L, (bf16_t*)yb,
+                         (int64_t)ldy);
+    else
+      hipLaunchKernelGGL(nct_to_ntc_pad_len_kernel<float>, grid, dim3(256), 0, s, xb, C, T_in, T, L, (float*)yb,
+                         (int64_t)ldy);
+  }
+  return launch_status(who);
+}
+
+extern "C" int vqx_index_mask_len(const int64_t* idx, int32_t B, int32_t T, const int32_t* len, int64_t* out,
+                                  int32_t T_out, vqx_stream_t stream) {
+  const char* who = "vqx_index_mask_len";
+  if (B < 1 || T < 1) { set_error("%s: B = %d, T = %d", who, B, T); return -1; }
+  if (T_out < 1 || T_out > T) { set_error("%s: T_out = %d outside [1, T = %d]", who, T_out, T); return -1; }
+  if ((int64_t)B * T > INT32_MAX) { set_error("%s: B*T = %lld must fit 31 bits", who, (long long)B * T); return -1; }
+  int Bc;
+  if (check_lens(who, len, (int64_t)B * T_out, T_out, Bc)) return -1;  // len[b] in 1..T_out
+  if (!idx || !out || ((uintptr_t)idx & 7) || ((uintptr_t)out & 7)) {
+    set_error("%s: null or unaligned (8 B) pointer", who);
+    return -1;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  for (int b0 = 0; b0 < B; b0 += kLenItems) {
+    const int n = std::min(kLenItems, B - b0);
+    const LenTable L = table_at(len, b0, n);
+    hipLaunchKernelGGL(index_mask_len_kernel, dim3(blocks_for(T_out), n), dim3(256), 0, s, idx + (int64_t)b0 * T, T, L,
+                       out + (int64_t)b0 * T_out, T_out);
   }
   return launch_status(who);
 }

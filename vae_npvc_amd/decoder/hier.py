@@ -1,5 +1,6 @@
-"""Voice conversion over a decode directory with the hierarchical model
-(`model_type: vae_npvc_amd.model.vqvae2`): `decoder.basic.Decoder` with the
+"""Voice conversion over a decode directory with a hierarchical model
+(`model_type: vae_npvc_amd.model.vqvae2`, `.vqvae2a` or `.vqvae2b`):
+`decoder.basic.Decoder` with the
 conversion step `model.convert((feat (1, mel, T), target (1, 1)))`, which takes
 utterances of any length one at a time.  A recipe selects it with
 

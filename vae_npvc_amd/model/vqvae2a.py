@@ -10,10 +10,12 @@ and `Decoder` of the hierarchical models, `upsample_cat`, `mean_pool`,
 fused log-loss, composed under torch autograd as `vqvae2.Model` composes
 them; what the three models share is `HierModelBase`.  There is no CPU path.
 """
+import torch
 import torch.nn as nn
 
+from .. import ops
 from .hier_base import HierModelBase
-from .hier_common import mean_pool, upsample_cat
+from .hier_common import DT, F32, mean_pool, upsample_cat
 from .hier_decoder import Decoder
 from .hier_encoder import Encoder
 from .layers import Conditions
@@ -36,7 +38,10 @@ class Model(HierModelBase):
     (one readback, at the end).  encode(x) restates :72-91.  convert((x, y_idx))
     is the xhat of the eval-mode forward, without gradients and without writing
     a parameter or buffer: the package's definition of conversion, which
-    `decoder_type: vae_npvc_amd.decoder.hier` drives.  Both are HierModelBase's.
+    `decoder_type: vae_npvc_amd.decoder.hier` drives.  Both are HierModelBase's,
+    and both take `lengths=` (host ints): a padded batch of utterances of
+    different lengths, each converted as it would be alone, on frame-major rows
+    throughout (`_render_lengths` is this model's decode side of it).
 
     Refused at construction: jitter_p != 0 with a mean-pooled quantized top
     level (one frame has no neighbour), a style-token top with a shared
@@ -132,6 +137,33 @@ class Model(HierModelBase):
                 xhat = self.decoders[i]((upsample_cat(cat, time), [y]))
         loss, losses = self._loss(xhat, x, level_losses, enc_losses, named)
         return xhat, loss, losses
+
+    def _embed(self, i):
+        return self.embeds[i] if self.use_embeds else self.embed
+
+    def _render_lengths(self, levels, ys, B, lens, lv):
+        """forward's top-down chain for a padded batch: decoder i's frame-major
+        input is one vqx_codes_upsample_cat_len launch over [level i's indices
+        (or the style rows), the upper decoder's f32 output rows], each
+        utterance stretched by its own factors; upsample_last leaves a
+        decoder's output at its own rate, and the launch that reads it next
+        stretches it (the bottom one by a launch of its own)."""
+        dt, dev = DT[self.compute_dtype], ys[0].device
+        out, out_len = None, None
+        for i in reversed(range(self.levels)):
+            # the frames the reference calls `time`: the level below's, x's at the bottom (levels == 1: the level's own)
+            time = lens if i == 0 and self.levels > 1 else lv[i - 1]
+            run = lv[i] if self.upsample_last else time
+            cat, cat_len = ([levels[i]], [lv[i]]) if out is None else ([levels[i], out], [lv[i], out_len])
+            Td, dec = max(run), self.decoders[i]
+            rows = torch.empty(B * Td, dec.layers[0].cin, device=dev, dtype=dt)
+            ops.codes_upsample_cat_len(cat, B, Td, run, cat_len, rows)
+            out, out_len = dec.forward_rows(rows, B, Td, [ys[i]], lengths=run), run
+        T = max(time)
+        if out_len != time:  # upsample_last: the bottom decoder's output, stretched to x's frames
+            out = ops.codes_upsample_cat_len([out], B, T, time, [out_len],
+                                             torch.empty(B * T, out.shape[1], device=dev, dtype=F32))
+        return ops.ntc_to_nct_len(out, T, time, torch.empty(B, out.shape[1], T, device=dev, dtype=F32))
 
     def decode(self, input, time=None):
         raise NotImplementedError("vqvae2a.Model.decode: the reference's version reads an undefined `x` at level 0 "

@@ -152,7 +152,9 @@ class Model(HierModelBase):
     (B, levels), level i rendered with speaker ys[:, i]; infer((x, ys)) is the
     two together.  convert((x, y_idx)) is the xhat of the eval-mode forward
     (encode and convert are HierModelBase's).  encode, decode, infer and
-    convert run without gradients and write no parameter or buffer.
+    convert run without gradients and write no parameter or buffer.  All four
+    take `lengths=` (host ints): a padded batch of utterances of different
+    lengths, each rendered as it would be alone (`_render_lengths`).
 
     Refused at construction: jitter_p != 0 with a mean-pooled quantized top
     level (one frame has no neighbour), use_gst with pooling_last: false (the
@@ -262,15 +264,65 @@ class Model(HierModelBase):
             raise ValueError(f"{who}: ys has speakers in {lo}..{hi}, the model has 0..{y_num - 1}")
         return zs, B, T
 
-    def decode(self, input, time=None):
+    def _render_lengths(self, levels, ys, B, lens, lv):
+        """decode's launches for a padded batch: every level decoder's input
+        from one vqx_codes_upsample_cat_len launch (at the level's own rate
+        with upsample_last, else at x's), the join one such launch over the L
+        f32 outputs, the final decoder and the output layout change, each
+        utterance with its own stretch factors."""
+        dt, dev = DT[self.compute_dtype], ys[0].device
+        outs, out_lens, T = [], [], max(lens)
+        for i in range(self.levels):
+            run = lv[i] if self.upsample_last else lens
+            Td, dec = max(run), self.decoders[i]
+            rows = torch.empty(B * Td, dec.layers[0].cin, device=dev, dtype=dt)
+            ops.codes_upsample_cat_len([levels[i]], B, Td, run, [lv[i]], rows)
+            outs.append(dec.forward_rows(rows, B, Td, [ys[i]], lengths=run))
+            out_lens.append(run)
+        joined = torch.empty(B * T, sum(o.shape[1] for o in outs), device=dev, dtype=dt)
+        ops.codes_upsample_cat_len(outs, B, T, lens, out_lens, joined)
+        xhat = self.final_decoder.forward_rows(joined, B, T, None, lengths=lens)
+        return ops.ntc_to_nct_len(xhat, T, lens, torch.empty(B, xhat.shape[1], T, device=dev, dtype=F32))
+
+    def _decode_lengths(self, zs, ys, time, lengths):
+        """decode for a padded batch: utterance b has lengths[b] output frames."""
+        who = "vqvae2b.Model.decode"
+        if not torch.is_tensor(ys) or ys.dim() != 2:
+            raise ValueError(f"{who}: ys must be int64 (B, levels) speaker indices")
+        lens = list(ops.len_array(lengths, ys.shape[0], f"{who} lengths"))
+        if min(lens) < 1:
+            raise ValueError(f"{who}: lengths[{lens.index(min(lens))}] = {min(lens)} is not a frame count")
+        lv = self.level_lengths(lens)
+        if time is not None and int(time) != max(lens):
+            raise ValueError(f"{who}: with lengths the output has max(lengths) = {max(lens)} frames; time = {time}")
+        zs = list(zs)
+        for i, z in enumerate(zs[:self.levels]):
+            if torch.is_tensor(z) and z.dim() >= 2 and z.shape[-1] != max(lv[i]):
+                raise ValueError(f"{who}: level {i} holds {z.shape[-1]} frames, encode(x, lengths) gives {max(lv[i])}")
+        zs, B, T = self._check_decode(zs, ys, max(lens))
+        if not all(z.is_cuda for z in zs) or not ys.is_cuda:
+            raise self._off_device()
+        with torch.no_grad():
+            levels = [zs[i].float().reshape(B, -1) if self._is_style(i) else self._index_level(i, zs[i])
+                      for i in range(self.levels)]
+            return self._render_lengths(levels, self._speaker_rows(ys), B, lens, lv)
+
+    def decode(self, input, time=None, lengths=None):
         """((zs, ys (B, levels)), time) -> xhat (B, mel, T) (vqvae2b.py:73-90):
         zs as `encode` returns them, level i rendered by decoders[i] with the
         speaker ys[:, i].  T = `time`, else the longest level.  A quantized
         level goes from its indices to its decoder's frame-major input in one
         vqx_codes_upsample_cat launch (a normalised codebook is normalised on
         the fly); everything up to xhat stays frame-major.  Under no_grad;
-        writes no parameter or buffer.  Bad arguments raise ValueError."""
+        writes no parameter or buffer.  Bad arguments raise ValueError.
+
+        lengths (host values, as encode): zs are the codes of a padded batch
+        as encode(x, lengths) returns them; xhat is (B, mel, max(lengths)) with
+        zeros at t >= lengths[b], each utterance rendered as it would be alone;
+        `time`, if given, must equal max(lengths)."""
         zs, ys = input
+        if lengths is not None:
+            return self._decode_lengths(zs, ys, time, lengths)
         zs, B, T = self._check_decode(zs, ys, time)
         if not all(z.is_cuda for z in zs) or not ys.is_cuda:
             raise self._off_device()
@@ -292,7 +344,14 @@ class Model(HierModelBase):
             ops.upsample_cat_fwd(outs, B, T, joined)
             return to_nct(self.final_decoder.forward_rows(joined, B, T, None), B, T)
 
-    def infer(self, input):
-        """(x, ys (B, levels)) -> decode((encode(x), ys)) (vqvae2b.py:93-97)."""
+    def infer(self, input, lengths=None):
+        """(x, ys (B, levels)) -> decode((encode(x), ys)) (vqvae2b.py:93-97);
+        with lengths, decode((encode(x, lengths), ys), lengths=lengths)."""
         x, ys = input
+        if lengths is not None:
+            B = x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else None
+            if not torch.is_tensor(ys) or ys.dim() != 2 or tuple(ys.shape) != (B, self.levels) or ys.dtype != torch.int64:
+                raise ValueError(f"vqvae2b.Model.infer: ys must be int64 (B, levels) = ({B}, {self.levels}) speaker "
+                                 "indices, one column per level")
+            return self.decode((self.encode(x, lengths), ys), lengths=lengths)
         return self.decode((self.encode(x), ys))

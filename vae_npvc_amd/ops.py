@@ -1312,6 +1312,43 @@ def ntc_to_nct_len(y, T, lengths, x_nct):
     return x_nct
 
 
+def nct_to_ntc_pad_len(x_nct, T, lengths, y):
+    """y[b*T + t, c] = x_nct[b, c, t] for t < lengths[b] <= T_in, else 0, over t < T >= T_in = x_nct.shape[2]
+    (vqx_nct_to_ntc_pad_len): nct_to_ntc_len into more rows an utterance than x has frames; x_nct is not read from
+    lengths[b] up.  Shapes and dtypes are checked before the device (ValueError)."""
+    if x_nct.dim() != 3 or x_nct.dtype != torch.float32 or not x_nct.is_contiguous():
+        raise ValueError("nct_to_ntc_pad_len: x must be a contiguous f32 (B, C, T_in) tensor")
+    B, C, T_in = x_nct.shape
+    if isinstance(T, bool) or not isinstance(T, int) or T < T_in:
+        raise ValueError(f"nct_to_ntc_pad_len: T = {T!r} rows an utterance must be an int >= x's {T_in} frames")
+    arr = len_array(lengths, B, "nct_to_ntc_pad_len lengths")
+    if y.dim() != 2 or y.shape[0] != B * T or y.shape[1] < C or y.stride(1) != 1 \
+            or y.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"nct_to_ntc_pad_len: y must be f32 or bf16 [{B * T}, >= {C}] rows with unit column stride")
+    _check_cuda(x_nct, y)
+    _rows(y, B * T, y.stride(0), C, "nct_to_ntc_pad_len y")
+    call("vqx_nct_to_ntc_pad_len", ptr(x_nct), B, C, T_in, T, arr, ptr(y), y.stride(0), dt_code(y.dtype), stream_ptr())
+    return y
+
+
+def index_mask_len(idx, lengths, out):
+    """out[b, t] = idx[b, t] for t < lengths[b], else 0, over t < T_out = out.shape[1] <= idx.shape[1]
+    (vqx_index_mask_len), both int64: the codes of a padded batch with zeros at the padded positions; idx is not read
+    from lengths[b] up.  Shapes and dtypes are checked before the device (ValueError)."""
+    if idx.dim() != 2 or idx.dtype != torch.int64 or not idx.is_contiguous():
+        raise ValueError("index_mask_len: idx must be a contiguous int64 (B, T) tensor")
+    B, T = idx.shape
+    if out.dim() != 2 or out.dtype != torch.int64 or not out.is_contiguous() or out.shape[0] != B \
+            or not 1 <= out.shape[1] <= T:
+        raise ValueError(f"index_mask_len: out must be a contiguous int64 ({B}, T_out <= {T}) tensor")
+    arr = len_array(lengths, B, "index_mask_len lengths")
+    _check_cuda(idx, out)
+    _span(idx, idx.numel(), "index_mask_len idx")
+    _span(out, out.numel(), "index_mask_len out")
+    call("vqx_index_mask_len", ptr(idx), B, T, arr, ptr(out), out.shape[1], stream_ptr())
+    return out
+
+
 def codes_upsample_cat_len(levels, B, T, lengths, level_lengths, out):
     """codes_upsample_cat for a padded batch (vqx_codes_upsample_cat_len): utterance
     b has lengths[b] <= T output frames and level_lengths[l][b] frames at level
