@@ -674,6 +674,14 @@ int vqx_radam_step(float* p, const float* g, float* m, float* v, int64_t n, cons
  *   inside [0, n_flat).  16-B accesses for a tensor whose p + offset,
  *   m + offset, v + offset and gradient are all 16-B aligned, single elements
  *   otherwise.
+ * multi_pack (data parallel; additive, the ABI version does not change):
+ *   flat[offset[i] + j] = grads[i][j] for every tensor, so that a collective
+ *   sees one flat gradient; a NULL gradient has its range zero-filled (no rank
+ *   sends uninitialised memory).  Same ranges rule as multi_adam_step, checked
+ *   before any launch; flat and the gradients 4-B aligned.  16-B loads and
+ *   stores for a tensor whose gradient and flat + offset are both 16-B
+ *   aligned, single elements otherwise.  ceil(n / VQX_MULTI_MAX_TENSORS)
+ *   launches.
  */
 #define VQX_MULTI_MAX_TENSORS 128
 #define VQX_MULTI_CHUNK 4096
@@ -683,6 +691,8 @@ int vqx_multi_sq_norm(const float* const* grads, const int64_t* numel, int32_t n
 int vqx_multi_adam_step(float* p, float* m, float* v, int64_t n_flat, const int64_t* offset,
                         const int64_t* numel, const float* const* grads, int32_t n, const float* hyper,
                         const float* sumsq, float max_norm, int32_t kind, vqx_stream_t stream);
+int vqx_multi_pack(float* flat, int64_t n_flat, const int64_t* offset, const int64_t* numel,
+                   const float* const* grads, int32_t n, vqx_stream_t stream);
 
 /*
  * Straight-through VectorQuantizer (use_ema: false; layers_vq.py:9-163,

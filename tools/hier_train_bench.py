@@ -15,9 +15,17 @@ per second from the algorithmic bytes (norm: g read once; Adam: p, g, m, v
 read and p, m, v written once) against the 8 TB/s HBM figure, and the number
 of launches of c.
 
+--ddp times the price of the data-parallel path itself instead (scaling over
+GPUs needs more than one): the whole step with a world-size-1 RCCL Comm
+attached (vqx_multi_pack, one AVG all-reduce of the flat gradient per bucket,
+the gradient views) against the step without one, two trainers in one process,
+alternating; and, on the gradients a step left behind, the pack launches alone
+and the pack + all-reduce + wait.  With the collectives, bytes and pack
+launches per step.
+
 Device events around windows of REPS iterations, the paths alternating, median
 and spread over the windows.  A lab script, no pass/fail bar.
-Usage (GPU box): python tools/hier_train_bench.py [--json OUT] [--dtypes fp32,bf16]"""
+Usage (GPU box): python tools/hier_train_bench.py [--json OUT] [--dtypes fp32,bf16] [--ddp]"""
 import argparse
 import json
 import os
@@ -134,16 +142,79 @@ def run(dtype):
     return res
 
 
+def run_ddp(dtype):
+    """The step with a world-size-1 RCCL Comm attached against the step without."""
+    import socket
+
+    import torch.distributed as dist
+
+    from vae_npvc_amd.parallel.ddp import Comm
+    if not dist.is_initialized():
+        with socket.socket() as s:
+            s.bind(("127.0.0.1", 0))
+            port = s.getsockname()[1]
+        dev = torch.device("cuda", torch.cuda.current_device())
+        dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1, device_id=dev)
+    cfg = recipe(dtype)
+    torch.manual_seed(0)
+    plain = Trainer(cfg)  # (world size 1: the Trainer attaches nothing)
+    ddp = Trainer(cfg)
+    ddp.model.load_state_dict(plain.model.state_dict())
+    comm = Comm()
+    eng = ddp.engine
+    eng.attach_comm(comm)
+    x = torch.randn(B, MEL, T, device="cuda")
+    y = torch.randint(0, cfg["y_num"], (B, 1), device="cuda")
+    n, nt = eng.n_params, len(eng.params)
+    res = {"dtype": dtype, "shape": dict(B=B, T=T, mel=MEL), "parameters": n, "tensors": nt, "reps": REPS,
+           "windows": WINDOWS, "backend": comm.backend, "world": comm.world}
+    res["step"] = timed({"plain": lambda: plain.train_step((x, y)), "comm_world1": lambda: ddp.train_step((x, y))},
+                        WARMUP, REPS, WINDOWS)
+    comm.reset_stats()
+    ddp.train_step((x, y))
+    torch.cuda.synchronize()
+    res["per_step"] = {"collectives": comm.calls, "bytes": comm.bytes, "pack_launches": -(-nt // ops.MULTI_MAX_TENSORS)}
+    # the added work alone, on the gradient tensors autograd left behind in the plain trainer
+    grads = plain.engine._grads()
+    eng.plan.set_grads(grads)
+
+    def pack_reduce_wait():
+        ops.multi_pack(eng.plan, eng.flat_g)
+        comm.grads_ready(eng.flat_g, 0, n)
+        comm.finish()
+
+    res["reduce"] = timed({"multi_pack": lambda: ops.multi_pack(eng.plan, eng.flat_g),
+                           "pack_allreduce_wait": pack_reduce_wait}, WARMUP, 10, WINDOWS)
+    r = res["reduce"]["multi_pack"]
+    r["algorithmic_bytes"] = 8 * n  # g read once, flat written once
+    r["bytes_per_s"] = 8 * n / (r["median_us"] * 1e-6)
+    r["fraction_of_hbm"] = r["bytes_per_s"] / HBM_BYTES_PER_S
+    for group in ("step", "reduce"):
+        for name, r in res[group].items():
+            extra = f", {r['bytes_per_s'] / 1e12:.2f} TB/s ({100 * r['fraction_of_hbm']:.0f}% of 8 TB/s)" \
+                if "bytes_per_s" in r else ""
+            print(f"{dtype} ddp {group} {name}: median {r['median_us'] / 1e3:.3f} ms (min {r['min_us'] / 1e3:.3f}, "
+                  f"max {r['max_us'] / 1e3:.3f}){extra}", flush=True)
+    a, b = res["step"]["plain"]["median_us"], res["step"]["comm_world1"]["median_us"]
+    res["step"]["added_us"] = b - a
+    print(f"{dtype} ddp: comm step - plain step = {(b - a) / 1e3:+.3f} ms; per step {res['per_step']}", flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
     ap.add_argument("--dtypes", default="fp32,bf16")
+    ap.add_argument("--ddp", action="store_true", help="time the data-parallel path (world-size-1 RCCL) instead")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "hier_train_bench needs the MI355X"
-    out = [run(d) for d in a.dtypes.split(",")]
+    out = [(run_ddp if a.ddp else run)(d) for d in a.dtypes.split(",")]
     if a.json:
         with open(a.json, "w") as f:
             json.dump(out, f, indent=1)
+    if a.ddp:
+        import torch.distributed as dist
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

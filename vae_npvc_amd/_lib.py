@@ -206,6 +206,7 @@ _SIGS = {
     "vqx_multi_sq_norm": [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p],
     "vqx_multi_adam_step": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
                             c_void_p, c_float, c_int32, c_void_p],
+    "vqx_multi_pack": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p],
     "vqx_gst_workspace": [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, ctypes.POINTER(c_int64)],
     "vqx_gst_fwd": [ctypes.POINTER(GstArgs), c_void_p],
     "vqx_gst_bwd": [ctypes.POINTER(GstArgs), c_void_p],

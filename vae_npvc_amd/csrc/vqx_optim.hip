@@ -1,6 +1,7 @@
 // The global gradient norm and the optimizers (gfx950): Adam, RAdam, Adam
 // fused with the next forward's weight-norm preparation, and the multi-tensor
-// pair for gradients that are separate tensors (flat p, m, v).
+// family for gradients that are separate tensors (flat p, m, v; the pack into
+// one flat gradient for a collective).
 #include "vqx_common.h"
 #include "vqx_wn_pack.h"
 #include <math.h>
@@ -588,6 +589,40 @@ __global__ __launch_bounds__(256) void multi_adam_kernel(float* __restrict__ p, 
   }
 }
 
+// vqx_multi_pack: flat[off_t + j] = g_t[j], a block per 4096-element chunk; a
+// tensor without a gradient has its range zero-filled.  16-B loads and stores
+// when the gradient and flat + off_t are both 16-B aligned (decided per tensor,
+// so uniform in a block), one element at a time otherwise.
+__global__ __launch_bounds__(256) void multi_pack_kernel(float* __restrict__ flat, MultiArgs A) {
+  const int b = blockIdx.x;
+  const int t = multi_find(A, b);
+  const float* __restrict__ g = A.g[t];
+  const int64_t len = A.numel[t];
+  const int64_t c0 = (int64_t)(b - A.blk[t]) * kMultiChunk;
+  float* __restrict__ dst = flat + A.off[t];
+  const bool al = ((((uintptr_t)dst) | ((uintptr_t)g)) & 15) == 0;  // (a null gradient counts as aligned)
+  if (al) {
+    f32x4_t x[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {  // every load first
+      const int64_t j = c0 + (int64_t)threadIdx.x * 4 + 1024 * u;
+      x[u] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+      if (g && j + 4 <= len) x[u] = *(const f32x4_t*)(g + j);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t j = c0 + (int64_t)threadIdx.x * 4 + 1024 * u;
+      if (j + 4 <= len) {
+        *(f32x4_t*)(dst + j) = x[u];
+      } else {
+        for (int64_t e = j; e < len && e < j + 4; ++e) dst[e] = g ? g[e] : 0.f;
+      }
+    }
+  } else {
+    for (int64_t j = c0 + threadIdx.x; j < len && j < c0 + kMultiChunk; j += 256) dst[j] = g ? g[j] : 0.f;
+  }
+}
+
 }  // namespace vqx
 
 using namespace vqx;
@@ -828,4 +863,47 @@ extern "C" int vqx_multi_adam_step(float* p, float* m, float* v, int64_t n_flat,
                          sumsq, max_norm, A);
   }
   return launch_status("vqx_multi_adam_step");
+}
+
+extern "C" int vqx_multi_pack(float* flat, int64_t n_flat, const int64_t* offset, const int64_t* numel,
+                              const float* const* grads, int32_t n, vqx_stream_t stream) {
+  if (!flat || n < 0 || n_flat < 0 || (n && (!offset || !numel || !grads))) {
+    set_error("vqx_multi_pack: bad arguments");
+    return -1;
+  }
+  if (((uintptr_t)flat) & 3) {
+    set_error("vqx_multi_pack: flat must be 4-B aligned");
+    return -1;
+  }
+  int64_t end = 0;
+  for (int i = 0; i < n; ++i) {  // ranges in order, inside [0, n_flat), not overlapping
+    if (numel[i] < 0) { set_error("vqx_multi_pack: tensor %d has a negative length", i); return -1; }
+    if (offset[i] < end || numel[i] > n_flat || offset[i] > n_flat - numel[i]) {
+      set_error("vqx_multi_pack: tensor %d: range out of order or out of [0, %lld)", i, (long long)n_flat);
+      return -1;
+    }
+    if (((uintptr_t)grads[i]) & 3) {
+      set_error("vqx_multi_pack: tensor %d: a gradient that is not 4-B aligned", i);
+      return -1;
+    }
+    end = offset[i] + numel[i];
+  }
+  for (int i0 = 0; i0 < n; i0 += kMultiMax) {
+    MultiArgs A;
+    A.n = 0;
+    A.blk[0] = 0;
+    for (int i = i0; i < n && i < i0 + kMultiMax; ++i) {
+      const int64_t ch = (numel[i] + kMultiChunk - 1) / kMultiChunk;
+      if (ch == 0) continue;
+      if ((int64_t)A.blk[A.n] + ch > 0x7fffffff) { set_error("vqx_multi_pack: too many chunks in one launch"); return -1; }
+      A.g[A.n] = grads[i];  // null: the range is zero-filled
+      A.off[A.n] = offset[i];
+      A.numel[A.n] = numel[i];
+      A.blk[A.n + 1] = A.blk[A.n] + (int)ch;
+      ++A.n;
+    }
+    if (A.n == 0) continue;
+    hipLaunchKernelGGL(multi_pack_kernel, dim3(A.blk[A.n]), dim3(256), 0, (hipStream_t)stream, flat, A);
+  }
+  return launch_status("vqx_multi_pack");
 }

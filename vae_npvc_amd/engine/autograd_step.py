@@ -9,6 +9,16 @@ It shows `Trainer` and `FusedOptimState` (trainer/basic.py) the surface of
 VQVAEEngine: params, flat_p, exp_avg, exp_avg_sq, opt_step, hyper, sumsq, lr0,
 sched_step, sched_gamma, betas, eps, opt_kind, device, init_optimizer,
 params_intact, invalidate_packed, attach_comm, train_step, optimizer_step.
+
+Data parallel (attach_comm with a parallel.ddp.Comm): after the backward the
+gradient tensors are packed into one flat buffer (vqx_multi_pack, zeros where
+a parameter has no gradient), mean all-reduced in the Comm's buckets, and
+every parameter that had a gradient gets its view of the buffer as .grad, so
+the clip and Adam run on the averaged gradient unchanged.  Autograd gives no
+per-group completion point, so both `grad_sync` values reduce after the
+backward: a reduction overlapped with the backward is not built (and nothing
+on a one-GPU box could measure it).  The EMA quantizer levels reduce their own
+statistics (model/layers_vq.py).
 """
 import torch
 
@@ -19,6 +29,8 @@ F32 = torch.float32
 
 class AutogradEngine:
     fused_forward = False  # Trainer.train_step: the step returns the model's loss dict, not a workspace
+    data_parallel = True   # Trainer._setup_engine: attach_comm takes a parallel.ddp.Comm
+    world, rank = 1, 0
 
     def __init__(self, model, device):
         self.m = model
@@ -57,8 +69,42 @@ class AutogradEngine:
         """Nothing is cached from the parameters between steps."""
 
     def attach_comm(self, comm):
-        raise NotImplementedError("data parallel is not built for the hierarchical model (vqvae2.Model): "
-                                  "run it on one device")
+        """Run the data-parallel path over `comm` (parallel/ddp.py Comm): the
+        flat gradient's mean all-reduce after the backward (reduce_grads) and,
+        in every EMAVectorQuantizer of the model, the global-batch codebook
+        statistics.  Anything else is refused."""
+        from ..model.layers_vq import EMAVectorQuantizer
+        from ..parallel.ddp import Comm
+        if not isinstance(comm, Comm):
+            raise NotImplementedError("data parallel for the hierarchical models runs over a parallel.ddp.Comm, not "
+                                      + type(comm).__name__)
+        self.comm, self.world, self.rank = comm, comm.world, comm.rank
+        self.flat_g = torch.zeros(self.n_params, device=self.device, dtype=F32)
+        # every parameter's view of flat_g, made once (about 450 slices a step would cost the host a millisecond)
+        self._g_views = [self.flat_g[off:off + p.numel()].view_as(p) for p, off in zip(self.params, self._p_off)]
+        for q in self.m.modules():
+            if isinstance(q, EMAVectorQuantizer):
+                q.attach_comm(comm)
+
+    def reduce_grads(self):
+        """Data parallel: the mean over ranks of every gradient.  Packs the
+        gradient tensors into flat_g (ceil(n / MULTI_MAX_TENSORS) launches;
+        zeros for a parameter without one, so every rank sends the same
+        ranges), all-reduces it in the Comm's buckets and makes the stream wait
+        for them, then hands every parameter that had a gradient its view of
+        flat_g.  A parameter without a gradient keeps None (Adam skips it, as
+        torch.optim.Adam does).  Nothing without a comm."""
+        if self.comm is None:
+            return
+        grads = self._grads()
+        self.plan.set_grads(grads)
+        ops.multi_pack(self.plan, self.flat_g)
+        self.comm.grads_ready(self.flat_g, 0, self.n_params)
+        self.comm.finish()
+        for p, g, view in zip(self.params, grads, self._g_views):
+            if g is not None:
+                p.grad = view
+        del grads
 
     # ------------------------------------------------------------ optimizer
     def init_optimizer(self, lr, betas=(0.5, 0.999), eps=1e-8, max_grad_norm=10.0, sched_step=None, sched_gamma=1.0,
@@ -121,12 +167,13 @@ class AutogradEngine:
 
     def train_step(self, x, y):
         """One training step (reference trainer/basic.py:55-79): forward and
-        backward under autograd, then optimizer_step().  Returns the model's
+        backward under autograd, [reduce_grads(),] then optimizer_step().  Returns the model's
         loss dict (its one readback happens at the end of the forward)."""
         for p in self.params:
             p.grad = None  # no zero-fill launches; autograd hands over its own tensors without an accumulate
         _, loss, detail = self.m((x, y))
         loss.backward()
+        self.reduce_grads()
         self.optimizer_step()
         return detail
 

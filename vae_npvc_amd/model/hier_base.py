@@ -36,8 +36,8 @@ class HierModelBase(nn.Module):
     def engine(self, device=None):
         """The optimizer engine of this package's Trainer (engine/autograd_step.py:
         flat parameters and moments, multi-tensor clip + Adam / RAdam; data
-        parallel refused), built once per device and rebuilt when the
-        parameters were moved."""
+        parallel over a parallel.ddp.Comm through its attach_comm), built once
+        per device and rebuilt when the parameters were moved."""
         dev = device if device is not None else next(self.parameters()).device
         dev = torch.device(dev)
         if dev.type != "cuda":

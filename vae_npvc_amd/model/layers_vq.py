@@ -17,21 +17,44 @@ from .. import ops
 F32 = torch.float32
 
 
-def draw_code_rows(zf, K):
+def draw_code_rows(zf, K, comm=None, summed=False):
     """The rows `_tile(z)[torch.randperm(len)][:K]` of init_emb / update_emb
     (layers_vq.py:183-190,197,213) for the frames zf [N, D], drawn from torch's
     CPU generator exactly as the reference draws them: `randn_like` when N < K,
     then `randperm`.  Returns (perm, None) with perm a host int32 [K] tensor of
     row numbers of zf when N >= K (zf's values are not read: no
     synchronisation), else (None, rows) with rows the K tiled noisy rows as a
-    host f32 tensor (zf is copied to the host; rare)."""
+    host f32 tensor (zf is copied to the host; rare).
+
+    comm (data parallel; anything with world, rank and all_gather_cat): zf is
+    this rank's equal shard of a global batch of N * world frames, rank r
+    owning the global rows [r * N, (r + 1) * N), and the generator is consumed
+    exactly as one process on the global batch consumes it, identically on
+    every rank.  With N * world >= K, perm holds this rank's local row numbers
+    and -1 for a row another rank owns (ops.gather_rows_host gives zero rows
+    there), so the SUM over ranks of the gathers is the global batch's rows.
+    Otherwise the tiling runs on the all_gather_cat of the ranks' frames and
+    every rank gets the same K rows; with `summed` (the rows go through a SUM
+    all-reduce) every rank but 0 gets zeros instead.  Needs no device."""
     N, D = zf.shape
-    if N >= K:
-        return torch.randperm(N)[:K].to(torch.int32), None
-    z = zf.detach().float().cpu()
-    zt = z.repeat((K + N - 1) // N, 1)
+    world = 1 if comm is None else comm.world
+    if N * world >= K:
+        perm = torch.randperm(N * world)[:K]
+        if comm is not None:
+            from ..parallel.ddp import owned_rows
+            perm = owned_rows(perm, comm.rank * N, N)
+        return perm.to(torch.int32), None
+    z = zf.detach().float()
+    if comm is not None:
+        z = comm.all_gather_cat(z)
+    z = z.cpu()
+    n = z.shape[0]
+    zt = z.repeat((K + n - 1) // n, 1)
     zt = zt + torch.randn_like(zt) * (0.01 / np.sqrt(D))
-    return None, zt[torch.randperm(zt.shape[0])][:K].contiguous()
+    rows = zt[torch.randperm(zt.shape[0])][:K].contiguous()
+    if summed and comm is not None and comm.rank != 0:
+        rows.zero_()
+    return None, rows
 
 
 def map_to_device(src_t, device):
@@ -58,6 +81,7 @@ class EMAVectorQuantizer(nn.Module):
         self.update = True
         self._init_host = None  # host mirror of emb_init (avoids a device sync per step)
         self.last_indices = None
+        self.comm = None  # data parallel: attach_comm
 
     @property
     def initialized(self):
@@ -72,6 +96,18 @@ class EMAVectorQuantizer(nn.Module):
     def _load_from_state_dict(self, *args, **kwargs):
         super()._load_from_state_dict(*args, **kwargs)
         self._init_host = None
+
+    def attach_comm(self, comm):
+        """Data parallel (parallel/ddp.py Comm, or None to detach): a training
+        forward that initialises or updates the codebook then uses the GLOBAL
+        batch, every rank holding an equal shard of it: init_emb's rows are
+        SUM-reduced into `embeddings`, and bsum | bcnt | rand_rows travel in
+        one SUM all-reduce per call between the lookup and the EMA update, so
+        the buffers, entropy, used_curr, usage and diff_emb are global and
+        equal on every rank.  The commitment loss stays the rank's own (the
+        mean over ranks is the global value).  An eval-mode forward, encode and
+        decode issue no collective."""
+        self.comm = comm
 
     def encode(self, z, time_last=True):
         """Nearest-code indices of z (B, D, T) (layers_vq.py:236-252) on the HIP VQ kernel."""
@@ -176,10 +212,13 @@ class _EMAQuantizeFn(torch.autograd.Function):
         E = q.embeddings
         if E.dtype != F32 or not E.is_contiguous():
             raise ValueError("EMAVectorQuantizer: the codebook buffer must be a contiguous f32 tensor")
+        comm = q.comm
         if q.training and not q.initialized:  # init_emb (:192-201)
-            perm, rows = draw_code_rows(zf, K)
+            perm, rows = draw_code_rows(zf, K, comm)
             if perm is not None:
                 ops.gather_rows_host(zf, perm, E)
+                if comm is not None:  # each rank filled the rows it owns
+                    comm.all_reduce_sum(E)
             else:
                 E.copy_(rows)
             ops.convert_2d(E, q.emb_sum)
@@ -189,7 +228,23 @@ class _EMAQuantizeFn(torch.autograd.Function):
         idx = torch.empty(N, device=dev, dtype=torch.int64)
         zq, sq = e(N, D), e(1)
         diag = None
-        if update:
+        if update and comm is not None:
+            # the global batch's statistics: bsum | bcnt | rand_rows in one bundle, one SUM
+            # all-reduce between the lookup and the update (on RCCL the wait is a stream wait)
+            bundle = ops.zero_(e(1, 2 * K * D + K)).view(-1)
+            bsum, bcnt = bundle[:K * D].view(K, D), bundle[K * D:K * D + K]
+            rand = bundle[K * D + K:].view(K, D)
+            ops.vq_forward(zf, E, idx, zq, None, sq, None, bsum, bcnt)
+            perm, rows = draw_code_rows(zf, K, comm, summed=True)  # update_emb's dead-code rows (:212-213)
+            if perm is not None:
+                ops.gather_rows_host(zf, perm, rand)
+            else:
+                rand.copy_(rows)
+            work = comm.all_reduce_sum(bundle, async_op=True)
+            diag = e(4)
+            comm.wait(work, "ema")
+            ops.vq_ema_update(q.emb_sum, q.emb_elem, E, bsum, bcnt, rand, q.mu, q.threshold, diag, q._workspace(dev))
+        elif update:
             counts = ops.zero_(e(1, K * D + K)).view(-1)
             bsum, bcnt = counts[:K * D].view(K, D), counts[K * D:]
             ops.vq_forward(zf, E, idx, zq, None, sq, None, bsum, bcnt)

@@ -964,6 +964,18 @@ def multi_adam_step(p, m, v, plan, hyper, sumsq, max_norm, kind=0):
          max_norm, kind, stream_ptr())
 
 
+def multi_pack(plan, flat):
+    """flat[offset_i : offset_i + numel_i] = gradient i of the plan (after
+    set_grads()), zeros where the gradient is missing: the one flat buffer a
+    collective reduces.  ceil(n / MULTI_MAX_TENSORS) launches."""
+    _check_cuda(flat)
+    if flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise ValueError("multi_pack: flat must be a contiguous float32 tensor")
+    call("vqx_multi_pack", ptr(flat), flat.numel(), ctypes.addressof(plan.offset_arr),
+         ctypes.addressof(plan.numel_arr), ctypes.addressof(plan.grad_arr), plan.n, stream_ptr())
+    return flat
+
+
 def convert_2d(src, dst, rows=None, cols=None):
     """dst[:rows, :cols] = src (dtype-converting, strided); src=None zero-fills."""
     rows = dst.shape[0] if rows is None else rows

@@ -9,15 +9,17 @@ with no host synchronisation; the optimizer state is saved in the
 torch.optim.Adam / reference RAdam state_dict format so reference checkpoints
 ({'model', 'optimizer', 'iteration'}) load both ways.
 
-`model_type: vae_npvc_amd.model.vqvae2` (the hierarchical model) has no fused
-forward: its forward and backward run under torch autograd and only the clip,
-Adam / RAdam and StepLR are fused (engine/autograd_step.py, the multi-tensor
-launches); train_step then returns the model's own loss dict.  Data parallel
-is not built for it and raises.
+`model_type: vae_npvc_amd.model.vqvae2 | vqvae2a | vqvae2b` (the hierarchical
+models) have no fused forward: forward and backward run under torch autograd
+and only the clip, Adam / RAdam and StepLR are fused (engine/autograd_step.py,
+the multi-tensor launches); train_step then returns the model's own loss dict.
 
 Data parallel: when torch.distributed is initialised, each rank trains on its
 own shard (per-rank batch) and the engine all-reduces gradients and EMA
-statistics (vae_npvc_amd/parallel/ddp.py).
+statistics (vae_npvc_amd/parallel/ddp.py).  The hierarchical models reduce
+the packed flat gradient after the backward, whatever `grad_sync` says
+(autograd gives no per-group completion point); an engine that has neither a
+fused forward nor `data_parallel` is refused.
 """
 from collections.abc import Mapping
 from importlib import import_module
@@ -203,9 +205,10 @@ class Trainer(object):
         optimizer moments."""
         self.engine = self.model.engine(self.device)
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            if not self._fused_forward():  # never train unsynchronised
-                raise NotImplementedError(f"{type(self.model).__module__}: data parallel is not built for the "
-                                          f"hierarchical model (world size {dist.get_world_size()}); run one process")
+            # never train unsynchronised
+            if not (self._fused_forward() or getattr(self.engine, "data_parallel", False)):
+                raise NotImplementedError(f"{type(self.model).__module__}: data parallel is not built for this "
+                                          f"engine (world size {dist.get_world_size()}); run one process")
             from ..parallel.ddp import Comm
             self.engine.attach_comm(Comm(overlap=self.grad_sync == "overlap"))
             dist.broadcast(self.engine.flat_p, 0)
