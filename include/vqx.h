@@ -1042,6 +1042,51 @@ int vqx_nct_to_ntc_pad_len(const float* x_nct, int32_t B, int32_t C, int32_t T_i
 int vqx_index_mask_len(const int64_t* idx, int32_t B, int32_t T, const int32_t* len, int64_t* out, int32_t T_out,
                        vqx_stream_t stream);
 
+/*
+ * Self-attention over latent frames (additive to ABI 130; the reference's
+ * MultiHeadedAttention, model/layers_gst.py:63-147, called as
+ * mha(x, x, x, key mask)): the part between the q/k/v GEMM and the output
+ * GEMM, per utterance b and head h of width d_k = F / H:
+ *   S   = q_h k_h^T / sqrt(d_k)  over the keys t2 < len[b]
+ *   P   = softmax over those keys;   ctx_h = P v_h
+ *   lse = log sum exp S per query row (all the forward saves beside qkv, ctx)
+ * which equals the reference's masked branch (masked_fill(min), softmax,
+ * masked_fill(0)) whenever len[b] >= 1.  `qkv` is the packed output of one
+ * GEMM: frame-major rows [B*T][ldqkv] in the compute dtype, q in columns
+ * [0, F), k in [F, 2F), v in [2F, 3F), head h in columns h*d_k .. (h+1)*d_k of
+ * each part.  vqx_attn_fwd: 1 launch, keys streamed in tiles with an online
+ * softmax (running maximum and sum per query row in f32), any T >= 1.
+ * vqx_attn_bwd: 3 launches: delta = rowsum(d_ctx * ctx) into `ws`; dK and dV
+ * of a 64-key tile held in accumulators over a sweep of the query tiles; dQ
+ * of a 64-query tile over a sweep of the key tiles.  Both recompute P from
+ * q, k and lse.  Each output is written by one workgroup: no atomics, no sum
+ * whose order depends on scheduling; equal arguments give equal bits.
+ * VQX_BF16 multiplies with mfma_f32_16x16x32_bf16 (f32 accumulation; scores,
+ * maxima and sums f32; P and dS rounded to bf16 only as MFMA operands),
+ * VQX_F32 with mfma_f32_16x16x4_f32 (P stays f32).  fp8 is not built.
+ * Rows t >= len[b] of qkv and d_ctx are never loaded (they may hold NaN);
+ * rows t >= len[b] of ctx and d_qkv are written as exact zeros (lse: 0).
+ * `len` is a host array of B entries in [1, T], validated before the first
+ * launch and passed by value (896 utterances a launch), or NULL (all T).
+ * Limits (else -1): B, T >= 1, B*T < 2^31; F % H == 0, d_k in {32, 64};
+ * ldqkv >= 3F, ldc >= F, both multiples of the 16-byte chunk; qkv, ctx, d_ctx,
+ * d_qkv 16-byte aligned; `ws` holds >= vqx_attn_workspace(...) floats (bwd).
+ */
+typedef struct {
+  const void* qkv;    /* [B*T][ldqkv], compute dtype                      */
+  void* ctx;          /* [B*T][ldc], F columns: fwd out, bwd in           */
+  float* lse;         /* [B][H][T]: fwd out, bwd in                       */
+  const void* d_ctx;  /* bwd in, layout of ctx                            */
+  void* d_qkv;        /* bwd out, layout of qkv                           */
+  float* ws;          /* bwd scratch                                      */
+  const int32_t* len; /* host, B entries, or NULL                         */
+  int32_t B, T, F, H, ldqkv, ldc, dtype;
+} vqx_attn_args;
+/* Host-only size query (floats) of the backward's workspace. */
+int vqx_attn_workspace(int32_t B, int32_t T, int32_t F, int32_t H, int32_t dtype, int64_t* floats);
+int vqx_attn_fwd(const vqx_attn_args* a, vqx_stream_t stream);
+int vqx_attn_bwd(const vqx_attn_args* a, vqx_stream_t stream);
+
 /* ABI 130: vqx_conv_args.rowbias_T appended (segmented row bias of the forward
  * epilogue; 0 or 1 keeps every earlier call's bits) and vqx_upsample_cat_*. */
 /* ABI version (major*100 + minor); VQX_ABI_VERSION is what this header describes. */

@@ -87,6 +87,15 @@ class GstArgs(ctypes.Structure):  # include/vqx.h vqx_gst_args
     ]
 
 
+class AttnArgs(ctypes.Structure):  # include/vqx.h vqx_attn_args
+    _fields_ = [
+        ("qkv", c_void_p), ("ctx", c_void_p), ("lse", c_void_p), ("d_ctx", c_void_p), ("d_qkv", c_void_p),
+        ("ws", c_void_p), ("len", c_void_p),
+        ("B", c_int32), ("T", c_int32), ("F", c_int32), ("H", c_int32), ("ldqkv", c_int32), ("ldc", c_int32),
+        ("dtype", c_int32),
+    ]
+
+
 class HierLevel(ctypes.Structure):  # include/vqx.h vqx_hier_level
     _fields_ = [("z", c_void_p), ("T_l", c_int32), ("C", c_int32), ("ld", c_int32)]
 
@@ -210,6 +219,9 @@ _SIGS = {
     "vqx_gst_workspace": [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, ctypes.POINTER(c_int64)],
     "vqx_gst_fwd": [ctypes.POINTER(GstArgs), c_void_p],
     "vqx_gst_bwd": [ctypes.POINTER(GstArgs), c_void_p],
+    "vqx_attn_workspace": [c_int32, c_int32, c_int32, c_int32, c_int32, ctypes.POINTER(c_int64)],
+    "vqx_attn_fwd": [ctypes.POINTER(AttnArgs), c_void_p],
+    "vqx_attn_bwd": [ctypes.POINTER(AttnArgs), c_void_p],
     "vqx_upsample_cat_fwd": [ctypes.POINTER(HierLevel), c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
                              c_void_p],
     "vqx_upsample_cat_bwd": [ctypes.POINTER(HierLevel), c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,

@@ -19,7 +19,8 @@ LIB = OUT_DIR / "libvqx.so"
 SOURCES = ["vqx_runtime.hip", "vqx_gemm.hip", "vqx_gemm_fwd.hip", "vqx_gemm_dgrad.hip", "vqx_gemm_wgrad.hip",
            "vqx_gemm_dual.hip",
            "vqx_vq.hip", "vqx_wn.hip", "vqx_gn.hip", "vqx_reduce.hip", "vqx_layout.hip", "vqx_data.hip", "vqx_loss.hip",
-           "vqx_linear.hip", "vqx_optim.hip", "vqx_gst.hip", "vqx_hier.hip", "vqx_varlen.hip"]
+           "vqx_linear.hip", "vqx_optim.hip", "vqx_gst.hip", "vqx_hier.hip", "vqx_varlen.hip",
+           "vqx_attn.hip"]
 HEADERS = ["vqx_common.h", "vqx_gemm_kernel.h", "vqx_gemm_inst.h", "vqx_gemm_pp.h", "vqx_gn_math.h", "vqx_vec.h",
            "vqx_wn_pack.h", str(ROOT / "include" / "vqx.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

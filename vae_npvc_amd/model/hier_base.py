@@ -65,6 +65,15 @@ class HierModelBase(nn.Module):
     def _pooled(self, i):
         return self.pooling_last and i == self.levels - 1
 
+    def _attend(self, i, z):
+        """Level i's encoder output z (B, C, T_i) as its pool / quantizer reads it (vqvae2a: attention.{i})."""
+        return z
+
+    def _attend_rows(self, i, z, B, T, lens):
+        """_attend on frame-major f32 rows z [B*T, C] of a padded batch whose
+        utterance b owns rows t < lens[b]; the other rows are undefined."""
+        return z
+
     # ------------------------------------------------------------ shared pieces
     def _off_device(self):
         return L.VqxError(f"{self.name} runs on the MI355X only (libvqx); move it and its inputs with .cuda()")
@@ -176,6 +185,7 @@ class HierModelBase(nn.Module):
         for i in range(self.levels):
             z, feat, Ti = self.encoders[i].forward_rows(feat, B, Ti, lengths=lin)
             lin = enc_len[i]
+            z = self._attend_rows(i, z, B, Ti, lin)
             q = self._quantizer(i)
             if self._is_style(i):
                 style = q.pool_rows(ops.segment_mean(z, Ti, lin, e(B, z.shape[1], dtype=F32)), 1)
@@ -231,6 +241,7 @@ class HierModelBase(nn.Module):
         with torch.no_grad():
             for i in range(self.levels):
                 z, x = self.encoders[i](x)
+                z = self._attend(i, z)
                 q = self._quantizer(i)
                 if self._is_style(i):
                     zs.append(q.pool_forward(z).unsqueeze(-1))

@@ -19,6 +19,7 @@ from .hier_common import DT, F32, mean_pool, upsample_cat
 from .hier_decoder import Decoder
 from .hier_encoder import Encoder
 from .layers import Conditions
+from .layers_attn import SelfAttention
 from .layers_gst import StyleTokenLayer
 from .layers_vq import EMAVectorQuantizer, Jitter, VectorQuantizer
 
@@ -33,6 +34,14 @@ class Model(HierModelBase):
     quantizer.{i} or quantizer (+ compute_dtype: fp32|bf16).  The module tree
     (encoders, decoders, quantizers | quantizer, embeds | embed, jitter), the
     parameter order and the state_dict keys are the reference's.
+
+    This package's addition: `attention.{i}: {n_head: H}` puts a residual
+    self-attention over level i's frames (layers_attn.SelfAttention, n_feat =
+    encoder.{i}'s z_channels) between that level's encoder and its pool /
+    quantizer: z = z + attention(z).  The layers are `attentions` (keys
+    attentions.{i}.mha.linear_{q,k,v,out}.{weight,bias}), registered after every
+    other module so that the order of the existing parameters does not move;
+    without such a key `attentions` does not exist.
 
     forward((x, y_idx)) restates vqvae2a.py:131-193: xhat, loss, loss dict
     (one readback, at the end).  encode(x) restates :72-91.  convert((x, y_idx))
@@ -86,6 +95,18 @@ class Model(HierModelBase):
         else:
             self.embed = Conditions(y_num, y_dim, normalize=False)
         self.jitter = Jitter(probability=jitter_p)
+        for key in arch:
+            if str(key).startswith("attention.") and key not in [f"attention.{i}" for i in range(levels)]:
+                raise ValueError(f"vqvae2a.Model: {key!r} names no level of 0..{levels - 1}")
+        attentions = {}
+        for i in range(levels):
+            if f"attention.{i}" in arch:
+                cfg = dict(arch[f"attention.{i}"])
+                if set(cfg) - {"n_head", "dropout_rate"} or "n_head" not in cfg:
+                    raise ValueError(f"vqvae2a.Model: attention.{i} takes n_head (and dropout_rate: 0), got {sorted(cfg)}")
+                attentions[str(i)] = SelfAttention(self.encoders[i].z_proj.cout, compute_dtype=dtype, **cfg)
+        if attentions:  # last: the order of the parameters above stays what it is without the key
+            self.attentions = nn.ModuleDict(attentions)
         self.beta = arch.get("beta", 0.01)
         self.pooling_last = pooling_last
         self.upsample_last = arch.get("upsample_last", False)
@@ -95,6 +116,18 @@ class Model(HierModelBase):
 
     def _quantizer(self, i):
         return self.quantizers[i] if self.use_quantizers else self.quantizer
+
+    def _attention(self, i):
+        att = getattr(self, "attentions", None)
+        return att[str(i)] if att is not None and str(i) in att else None
+
+    def _attend(self, i, z):
+        att = self._attention(i)
+        return z if att is None else att(z, residual=True)
+
+    def _attend_rows(self, i, z, B, T, lens):
+        att = self._attention(i)
+        return z if att is None else att.forward_rows(z, B, T, lengths=lens, residual=True)
 
     def forward(self, input):
         """(x (B, mel, T), y_idx (B, 1)) -> (xhat (B, mel, T), loss, loss dict).
@@ -110,6 +143,7 @@ class Model(HierModelBase):
         feat = x
         for i in range(self.levels):
             z, feat = self.encoders[i](feat)
+            z = self._attend(i, z)
             q = self._quantizer(i)
             if self._is_style(i):  # pooling_last is forced: the fused pool + attention
                 z_vq = q.pool_forward(z).unsqueeze(-1)

@@ -1111,6 +1111,59 @@ def gst_bwd(z, T, params, heads, d_style, ws, dz, grads):
     return dz
 
 
+def attn_workspace(B, T, F, H, dtype):
+    """Floats of attn_bwd's workspace (vqx_attn_workspace); raises for a shape the kernels refuse."""
+    out = ctypes.c_int64()
+    call("vqx_attn_workspace", int(B), int(T), int(F), int(H), dt_code(dtype), ctypes.byref(out))
+    return out.value
+
+
+def _attn_args(qkv, ctx, lse, B, T, H, lengths, what):
+    """vqx_attn_args of both directions.  qkv [B*T, >= 3F] rows (q | k | v) and
+    ctx [B*T, >= F] rows of one compute dtype with unit column stride, lse f32
+    of B*H*T entries; lengths: None or what len_array takes (host values)."""
+    arr = None if lengths is None else len_array(lengths, B, f"{what} lengths")  # before any device work
+    _check_cuda(qkv, ctx, lse)
+    if qkv.dim() != 2 or ctx.dim() != 2 or qkv.stride(1) != 1 or ctx.stride(1) != 1 or qkv.dtype != ctx.dtype \
+            or qkv.shape[0] != B * T or ctx.shape[0] != B * T or qkv.shape[1] % 3:
+        raise ValueError(f"{what}: qkv must be [{B * T}, 3F] rows and ctx [{B * T}, F] rows of one dtype")
+    F = qkv.shape[1] // 3
+    if ctx.shape[1] != F or lse.dtype != torch.float32 or lse.numel() < B * H * T or not lse.is_contiguous():
+        raise ValueError(f"{what}: ctx must have F = {F} columns, lse {B * H * T} contiguous f32 entries")
+    a = L.AttnArgs()
+    a.qkv, a.ctx, a.lse = ptr(qkv), ptr(ctx), ptr(lse)
+    a.len = ctypes.cast(arr, ctypes.c_void_p) if arr is not None else None  # the caller keeps arr alive over the call
+    a.B, a.T, a.F, a.H, a.ldqkv, a.ldc, a.dtype = B, T, F, H, qkv.stride(0), ctx.stride(0), dt_code(qkv.dtype)
+    _rows(qkv, B * T, a.ldqkv, 3 * F, f"{what} qkv")
+    _rows(ctx, B * T, a.ldc, F, f"{what} ctx")
+    return a, arr
+
+
+def attn_fwd(qkv, ctx, lse, B, T, H, lengths=None):
+    """ctx = softmax(q k^T / sqrt(d_k)) v per head over the keys t2 < lengths[b],
+    lse its log-sum-exp (vqx_attn_fwd, 1 launch); ctx rows t >= lengths[b] are zeros."""
+    a, arr = _attn_args(qkv, ctx, lse, B, T, H, lengths, "attn_fwd")
+    call("vqx_attn_fwd", ctypes.byref(a), stream_ptr())
+    return ctx
+
+
+def attn_bwd(qkv, ctx, lse, d_ctx, d_qkv, ws, B, T, H, lengths=None):
+    """d_qkv (overwritten) from d_ctx and what attn_fwd left (vqx_attn_bwd, 3
+    launches, no atomics); rows t >= lengths[b] of d_ctx are not read and those
+    of d_qkv are zeros.  ws: attn_workspace floats."""
+    a, arr = _attn_args(qkv, ctx, lse, B, T, H, lengths, "attn_bwd")
+    _check_cuda(d_ctx, d_qkv, ws)
+    if d_ctx.shape != ctx.shape or d_ctx.stride() != ctx.stride() or d_ctx.dtype != ctx.dtype \
+            or d_qkv.shape != qkv.shape or d_qkv.stride() != qkv.stride() or d_qkv.dtype != qkv.dtype:
+        raise ValueError("attn_bwd: d_ctx and d_qkv must have the shape, strides and dtype of ctx and qkv")
+    need = attn_workspace(B, T, a.F, H, qkv.dtype)
+    if ws.dtype != torch.float32 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError(f"attn_bwd: workspace {ws.numel()} < {need} floats")
+    a.d_ctx, a.d_qkv, a.ws = ptr(d_ctx), ptr(d_qkv), ptr(ws)
+    call("vqx_attn_bwd", ctypes.byref(a), stream_ptr())
+    return d_qkv
+
+
 HIER_MAX_LEVELS = 8  # include/vqx.h vqx_upsample_cat_*
 
 
